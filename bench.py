@@ -8,11 +8,20 @@
 
 A "step" is one pass of ``Pipeline(test=True).forward`` over one batch of synthetic reference
 views that is already resident in HBM.  One process per GPU, reference views sharded over the
-ranks with no data-path collective (weak scaling); the timed region is bracketed by a barrier +
-device synchronise and the maximum over ranks is reported.  Rank 0 prints ONE JSON line with
-the throughput, the HBM roofline of the dominant hand-written kernel (itermvs_corr_iter, timed
-with HIP events on its launch stream inside the timed region) and a CPU baseline (the oracle,
+ranks with no data-path collective (weak scaling); the timed region of exactly ``--steps`` steps
+(``--repeats`` regions, default 1) is bracketed by a barrier + device synchronise and the maximum
+over ranks is reported.  Rank 0 prints ONE JSON line with the throughput and ``ms_per_step``.
+
+A plain run does only that.  ``--full`` adds everything measured beside the headline: the HBM
+roofline of the dominant hand-written kernel (itermvs_corr_iter, timed with HIP events inside the
+timed region), the box calibration, the staged-input, pipelined and host-transfer legs, the
+convolution roofline pass, the other BASELINE configurations and a CPU baseline (the oracle,
 ``kind: port``, timed on this box's host cores over a bounded sample of the same workload).
+
+``--dump-outputs DIR`` writes the depth and confidence maps of the last timed step as float32
+``DIR/<name>.npy`` (rank r > 0: ``<name>_rank<r>.npy``); the inputs and weights are seeded, so two
+builds can be compared output for output.  Beyond 64 MB in all, each array is replaced by the
+same seeded sample of its elements.
 """
 from __future__ import annotations
 
@@ -74,6 +83,24 @@ def self_launch_command(n_gpus: int, argv):
         port = sk.getsockname()[1]
     return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n_gpus}",
             "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + list(argv)
+
+
+DUMP_BYTES = 64 << 20
+
+
+def write_outputs(out_dir: str, arrays, rank: int, world: int) -> None:
+    """``arrays`` (name -> float32 numpy array) as ``out_dir/<name>.npy`` (rank r > 0: ``<name>_rank<r>.npy``).  Beyond
+    DUMP_BYTES over all ranks, every array is cut to the same fixed, seeded sample of its flattened elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BYTES // world
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > budget:
+            keep = a.size * budget // total
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + (f"_rank{rank}" if rank else "") + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def cpu_baseline(args, target_seconds: float = 15.0):
@@ -225,21 +252,29 @@ def main() -> None:
                          "exact fp32 MFMA (A/B on one box)")
     ap.add_argument("--side-branch", action="store_true",
                     help="A/B: ref_quarter and the up-sampling-weight launch as a parallel graph branch (measured slower: profiles/r06)")
-    ap.add_argument("--repeats", type=int, default=9,
+    ap.add_argument("--repeats", type=int, default=1,
                     help="the --steps long timed region (barrier + device synchronise on both sides) is run this many times back "
                          "to back; `value` / `ms_per_step` are the MEDIAN region, min / max are reported beside them")
+    ap.add_argument("--full", action="store_true",
+                    help="every measurement beside the headline (roofline, box calibration, staged / pipelined / transfer legs, "
+                         "conv roofline, other BASELINE configs, CPU baseline); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the depth / confidence maps of the last timed step as float32 DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-transfers", action="store_true", help="skip the host-buffers-in / host-buffers-out leg")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the `other_configs` legs (BASELINE cfg 3 / cfg 5 shapes, cfg 4 training step) run after the timed region")
     ap.add_argument("--minimal", action="store_true",
-                    help="only the timed region (no CPU baseline, pipelined / transfer legs, conv roofline pass): profiling runs")
+                    help="with --full: only the timed region (no CPU baseline, pipelined / transfer legs, conv roofline pass) "
+                         "with its in-region timing and box probes")
     ap.add_argument("--streams", type=int, default=1,
                     help="independent reference views in flight per GPU (one HIP stream + engine workspace each)")
     ap.add_argument("--eager", action="store_true", help="launch kernel by kernel instead of replaying hipGraph segments")
     ap.add_argument("--pipeline-streams", type=int, default=4,
                     help="extra measurement: throughput with this many reference views in flight (0/1 = skip)")
     args = ap.parse_args()
+    if not args.full:           # the headline only: every leg --minimal drops, and the in-region timing and box probes as well
+        args.minimal = True
     if args.minimal:
         args.no_cpu_baseline = args.no_transfers = args.no_other_configs = True
         args.pipeline_streams = 0
@@ -267,10 +302,10 @@ def main() -> None:
     # box calibration (two fixed micro-kernels, <= 0.3 s): what THIS chip delivers, printed beside `value` so that driver
     # lines from different boxes of the pool can be compared (`value_normalised`)
     from itermvs_amd import benchmarks as _bm
-    box = _bm.box_probe(dev) if rank == 0 else None
+    box = _bm.box_probe(dev) if rank == 0 and args.full else None
 
     # graph mode, one stream: EIGHT runners replayed round-robin on that stream, each bound to one of the four resident samples
-    # (see `resident` below).  Runners 0 and 1 carry event-record nodes around one / two of their fused correlation launches;
+    # (see `resident` below).  With --full, runners 0 and 1 carry event-record nodes around one / two of their fused correlation launches;
     # while step i runs, the pairs of step i-1 are read, so the launches are measured inside the timed region without ever
     # draining the stream.  A bracket costs ~5 us of graph time: with three brackets spread over eight runners the timing
     # costs `value` ~1.9 us per step (it was 3.75 us with four runners in rounds 4-5).
@@ -322,16 +357,18 @@ def main() -> None:
         with torch.cuda.stream(streams[k]):
             out = models[k](imgs, projs, dmin, dmax)      # graph mode: one hipGraph replay on this stream
         sink[:] = [out["depths_upsampled"], out["confidence_upsampled"]]
-        if ab > 1 and i >= 1:
+        if args.full and ab > 1 and i >= 1:
             read_pairs(i - 1)
 
-    # HIP-event pairs around the fused kernels' launches (on their launch stream).  Graph mode: external
+    # --full: HIP-event pairs around the fused kernels' launches (on their launch stream).  Graph mode: external
     # event-record nodes captured with the launches (enabled BEFORE the capture below); eager mode: plain records.
+    # A plain run enables no profiling: its graphs carry no event-record nodes.
     per_step = args.iters + 1
     # (graph mode: an event-record node costs ~5-6 us of graph time on either side of the launch it brackets, so each replay
     # carries ONE timed launch: runner A a corr_iter (GRU iteration 1), runner B the corr_init)
     total_steps = args.steps * args.repeats
-    ops.profile_enable((total_steps + args.warmup) * per_step + 8 * per_step, mask=0x3)
+    if args.full:
+        ops.profile_enable((total_steps + args.warmup) * per_step + 8 * per_step, mask=0x3)
     for k in range(n_models):                          # set-up, not a step: capture every runner's hipGraph
         with torch.cuda.stream(streams[k]):
             if ab > 1:
@@ -355,19 +392,24 @@ def main() -> None:
 
     regions = shard.timed_regions(step, args.steps, args.warmup, args.repeats)
     elapsed = shard.median(regions)                    # the contract's K-step region; median of --repeats of them
+    outputs = None
+    if args.dump_outputs:       # the last timed step's maps, copied before anything below replays a runner or refills its inputs
+        outputs = {k: t.float().cpu().numpy() for k, t in zip(("depths_upsampled", "confidence_upsampled"), sink)}
     # this rank's own clock around the same regions (timed_regions reports the max over ranks): a straggler GPU shows up as
     # min < max across ranks in SCALE_r*.json
     own_ms = shard.median(shard.last_local_regions()) / args.steps * 1e3
     rank_ms = shard.gather_over_ranks(own_ms)
-    if ab > 1:
-        read_pairs(args.warmup + total_steps - 1)
-        prof = graph_prof
-    else:
-        prof = ops.profile_collect(max_samples=(total_steps + args.warmup) * per_step + 8 * per_step)[-total_steps * per_step:]
-    ops.profile_enable(0)
+    prof = []
+    if args.full:
+        if ab > 1:
+            read_pairs(args.warmup + total_steps - 1)
+            prof = graph_prof
+        else:
+            prof = ops.profile_collect(max_samples=(total_steps + args.warmup) * per_step + 8 * per_step)[-total_steps * per_step:]
+        ops.profile_enable(0)
     # the shader clock this chip holds under the timed workload itself (20 more steps between two counter stamps, rank 0)
     sclk_workload = None
-    if rank == 0:
+    if rank == 0 and args.full:
         counter = iter(range(10 ** 9))
 
         def plain_step() -> None:                      # a step without the event read-back of the timed region
@@ -532,12 +574,10 @@ def main() -> None:
                 other[name] = {"error": f"{type(e).__name__}: {e}"[:200]}
             torch.cuda.empty_cache()
 
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs, rank, world)
+
     if rank == 0:
-        # the probe once more after everything timed above: the chip's clocks drift with its thermal state within a run
-        box_end = _bm.box_probe(dev)
-        box_start = box
-        box = {k: 0.5 * (box_start[k] + box_end[k]) for k in box_start}
-        box["sclk_workload_MHz"] = sclk_workload
         result = {
             "metric": f"depth-maps/sec (ref-views/s) at {args.views}-view {args.width}x{args.height}, {args.iters} iters",
             "value": value, "unit": "depth-maps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -545,16 +585,13 @@ def main() -> None:
             "repeats": args.repeats, "ms_per_step_min": min(regions) / args.steps * 1e3,
             "ms_per_step_max": max(regions) / args.steps * 1e3,
             "ms_per_step_regions": [round(r / args.steps * 1e3, 5) for r in regions],     # every timed region, in order (`value` = their median)
-            # SURVEY 8(d) / eval.py:130-137 form of the same metric: pinned host buffers in (uint8 images as decoded from
-            # disk, cameras, depth range), pinned host buffers out (depth + confidence), copies overlapped with compute
-            "value_with_transfers": None,
             "vs_baseline": None, "dtype": "f32" if args.feature_dtype == "fp32" else f"f32 arithmetic, {args.feature_dtype} feature storage",
             "data": "synthetic",
             "config": {"workload": f"{workload_name(args.views, args.height, args.width, args.iters)}: 1 ref + {s_views} src views, "
                                    f"{args.width}x{args.height}, {args.iters} GRU iterations, test mode, "
                                    f"random-init weights, {args.batch} ref view(s) per step and GPU",
                        "views": args.views, "height": args.height, "width": args.width, "iterations": args.iters,
-                       "value_is": "inputs resident in HBM; `value_with_transfers` = host buffers in / out",
+                       "value_is": "inputs resident in HBM; `value_with_transfers` (--full) = host buffers in / out",
                        "batch_per_gpu": args.batch, "streams_per_gpu": args.streams, "feature_dtype": args.feature_dtype,
                        "launch": "eager" if args.eager else "one hipGraph per depth map",
                        "parallelism": f"ref-view sharding x{world}, no collective",
@@ -564,26 +601,37 @@ def main() -> None:
                        "cpu_affinity": affinity,
                        "algorithmic_MB_per_depth_map": b_map / 1e6},
             "ms_per_step_ranks": {"min": min(rank_ms), "max": max(rank_ms)},   # each rank's own median region (straggler check)
-            # this box against the pool (benchmarks.POOL_MEDIAN): `value` x (pool median / this box), per probe
-            "box": box, "box_start_end": [box_start, box_end], "value_normalised": _bm.normalised(value, box, roofline["avg_launch_ms"] if roofline and (args.views, args.height, args.width, args.iters, args.feature_dtype, args.batch) == (5, 512, 640, 4, "fp32", 1) else None),
-            "box_pool_median": _bm.POOL_MEDIAN,
-            "roofline": roofline,
-            "other_configs": other,
-            "roofline_conv": conv_roofline,
-            "staged_inputs": staged,
-            "pipelined": pipelined,
-            "with_transfers": with_transfers,
         }
-        if with_transfers is not None:
-            result["value_with_transfers"] = with_transfers.get("uint8_images", with_transfers)["value"]
-        if world == 1 and not args.no_cpu_baseline:
-            shard.restore_affinity()                   # the CPU path gets the whole host, not the GPU's NUMA node
-            result["cpu_baseline"] = cpu_baseline(args)
-            result["speedup_vs_cpu_baseline"] = value / result["cpu_baseline"]["value"]
-        elif world > 1:
-            # (the CPU port, the other BASELINE shapes and the training legs are timed on rank 0 of a 1-GPU run only)
-            result["cpu_baseline"] = "world>1: see the N=1 line"
-            result["other_configs"] = "world>1: see the N=1 line"
+        if args.full:
+            # the probe once more after everything timed above: the chip's clocks drift with its thermal state within a run
+            box_end = _bm.box_probe(dev)
+            box_start = box
+            box = {k: 0.5 * (box_start[k] + box_end[k]) for k in box_start}
+            box["sclk_workload_MHz"] = sclk_workload
+            result.update({
+                # SURVEY 8(d) / eval.py:130-137 form of the same metric: pinned host buffers in (uint8 images as decoded from
+                # disk, cameras, depth range), pinned host buffers out (depth + confidence), copies overlapped with compute
+                "value_with_transfers": None,
+                # this box against the pool (benchmarks.POOL_MEDIAN): `value` x (pool median / this box), per probe
+                "box": box, "box_start_end": [box_start, box_end], "value_normalised": _bm.normalised(value, box, roofline["avg_launch_ms"] if roofline and (args.views, args.height, args.width, args.iters, args.feature_dtype, args.batch) == (5, 512, 640, 4, "fp32", 1) else None),
+                "box_pool_median": _bm.POOL_MEDIAN,
+                "roofline": roofline,
+                "other_configs": other,
+                "roofline_conv": conv_roofline,
+                "staged_inputs": staged,
+                "pipelined": pipelined,
+                "with_transfers": with_transfers,
+            })
+            if with_transfers is not None:
+                result["value_with_transfers"] = with_transfers.get("uint8_images", with_transfers)["value"]
+            if world == 1 and not args.no_cpu_baseline:
+                shard.restore_affinity()                   # the CPU path gets the whole host, not the GPU's NUMA node
+                result["cpu_baseline"] = cpu_baseline(args)
+                result["speedup_vs_cpu_baseline"] = value / result["cpu_baseline"]["value"]
+            elif world > 1:
+                # (the CPU port, the other BASELINE shapes and the training legs are timed on rank 0 of a 1-GPU run only)
+                result["cpu_baseline"] = "world>1: see the N=1 line"
+                result["other_configs"] = "world>1: see the N=1 line"
         # the driver keeps the tail of stdout: 6 significant digits on everything but the headline numbers keeps the line short
         keep = {k: result[k] for k in ("value", "ms_per_step")}
         result = _round_floats(result)

@@ -69,6 +69,34 @@ def load_weights(tag):
     return {k: g[k] for k in g.keys()}
 
 
+def compose_key(src_proj, ref_proj):
+    """content key of one ``src_proj @ inverse(ref_proj)`` composition in tests/golden/compose_proj.npz"""
+    import hashlib
+    h = hashlib.sha1()
+    for t in (src_proj, ref_proj):
+        t = t.detach().float().contiguous().cpu()
+        h.update(repr(tuple(t.shape)).encode())
+        h.update(t.numpy().tobytes())
+    return h.hexdigest()
+
+
+@pytest.fixture
+def golden_host_projection(monkeypatch):
+    """The oracle's ``src @ inverse(ref)`` (module.py:77-87) as the host the golden vectors were captured on rounded it.
+    LAPACK / BLAS round that 4x4 inverse and product differently on other CPUs (an AMD EPYC moves ~1e-3 of the composed
+    entries), and the trained network turns that into arg-max flips far beyond the goldens' tolerances.  The compositions
+    of the fixtures' inputs are stored (tests/golden/make_golden.py compose); a composition not stored is an error."""
+    from oracle import itermvs_oracle as O
+    table = golden("compose_proj.npz")
+
+    def compose(src_proj, ref_proj):
+        key = compose_key(src_proj, ref_proj)
+        assert key in table, "projection not in tests/golden/compose_proj.npz: rerun tests/golden/make_golden.py compose"
+        return table[key].to(src_proj.device)
+
+    monkeypatch.setattr(O, "compose_projection", compose)
+
+
 @pytest.fixture(scope="session")
 def weights_seed0():
     return load_weights("seed0")

@@ -442,6 +442,32 @@ def golden_train_cfg4_b2(weights):
 
 
 # ----------------------------------------------------------------------------
+# 6d. src @ inverse(ref) (module.py:77-87) of every level and source view of the e2e and cfg-4 training inputs, as this
+#     host's LAPACK / BLAS round it: other CPUs round that 4x4 algebra differently, so the oracle checks of those fixtures
+#     replay the stored compositions (tests/conftest.py: golden_host_projection).  Keyed by conftest.compose_key.
+# ----------------------------------------------------------------------------
+def golden_compose():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from conftest import compose_key
+    from oracle import itermvs_oracle as O
+    cases = []
+    for tag in ("seed0", "dtu"):
+        z = np.load(os.path.join(HERE, f"e2e_small_{tag}.npz"))
+        cases.append([torch.from_numpy(z[f"proj.level_{l}"]) for l in (1, 2, 3)])
+    sample, _, _ = synthetic.make_training_sample(num_views=5, height=512, width=640, seed=2)
+    cases.append([sample["proj_matrices"][f"level_{l}"] for l in (1, 2, 3)])
+    _, projs, _, _, _, _ = synthetic.make_training_batch(2, num_views=5, height=512, width=640, seed=2, hole_fraction=0.1)
+    cases.append([projs[f"level_{l}"] for l in (1, 2, 3)])
+    table = {}
+    for case in cases:
+        for p in case:
+            p = p.float()
+            for i in range(1, p.shape[1]):
+                table[compose_key(p[:, i], p[:, 0])] = npy(O.compose_projection(p[:, i], p[:, 0]))
+    save("compose_proj.npz", **table)
+
+
+# ----------------------------------------------------------------------------
 # 7. PFM bytes as written by the reference's datasets/data_io.py (run separately: this part needs only numpy)
 # ----------------------------------------------------------------------------
 def golden_pfm():
@@ -486,6 +512,8 @@ def main():
         golden_train_cfg4(w0)
     if want("train_cfg4_b2"):
         golden_train_cfg4_b2(w0)
+    if want("compose"):
+        golden_compose()
     if want("pfm"):
         golden_pfm()
 

@@ -300,6 +300,27 @@ def test_bench_self_launch_and_workload_names():
     assert bench.workload_name(3, 64, 96, 2).startswith("custom")
 
 
+def test_bench_dump_outputs_stay_within_their_budget(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs`: whole float32 arrays while they fit, the same seeded element sample of each once they do not"""
+    import numpy as np
+    import bench
+    gen = np.random.default_rng(1)
+    arrays = {"depths_upsampled": gen.random((1, 1, 64, 96), dtype=np.float32),
+              "confidence_upsampled": gen.random((1, 1, 64, 96), dtype=np.float32)}
+    bench.write_outputs(str(tmp_path / "whole"), arrays, rank=0, world=1)
+    for name, a in arrays.items():
+        assert np.array_equal(np.load(tmp_path / "whole" / f"{name}.npy"), a)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8 * 1024)
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), arrays, rank=1, world=2)
+    got = {n: np.load(tmp_path / "a" / f"{n}_rank1.npy") for n in arrays}
+    assert sum(g.nbytes for g in got.values()) <= 4 * 1024
+    for name, a in arrays.items():
+        assert got[name].dtype == np.float32 and got[name].size > 0
+        assert np.isin(got[name], a).all()
+        assert np.array_equal(got[name], np.load(tmp_path / "b" / f"{name}_rank1.npy"))
+
+
 def test_timed_regions_and_median():
     from itermvs_amd import shard
     calls = []

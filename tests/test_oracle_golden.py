@@ -157,7 +157,7 @@ def test_update_seam(tag):
 
 
 @pytest.mark.parametrize("tag", ["seed0", "dtu"])
-def test_pipeline_small_end_to_end(tag):
+def test_pipeline_small_end_to_end(tag, golden_host_projection):
     g = golden(f"e2e_small_{tag}.npz")
     w = load_weights(tag)
     imgs = {"level_0": g["imgs"]}
@@ -255,7 +255,7 @@ def test_train_step_loss_and_grads(weights_seed0):
             assert maxdiff(w["feature_net.conv1.bn.running_mean"].detach(), g["train.running_mean_conv1"]) <= 1e-6
 
 
-def test_train_step_cfg4_full_size(weights_seed0):
+def test_train_step_cfg4_full_size(weights_seed0, golden_host_projection):
     """BASELINE cfg 4 at its real size (B=1, 5 views, 640x512, 4 iterations): loss and all 102 gradient norms of the
     reference's training step (tests/golden/train_cfg4.npz); inputs regenerated from seeds"""
     from itermvs_amd import synthetic
@@ -283,7 +283,7 @@ def test_train_step_cfg4_full_size(weights_seed0):
     assert float(rel.median()) <= 1e-6 and float((rel > 1e-4).float().mean()) <= 0.02
 
 
-def test_train_step_cfg4_batch2(weights_seed0):
+def test_train_step_cfg4_batch2(weights_seed0, golden_host_projection):
     """the same step at B = 2 (two scenes; the reference's `batch == 2` branch of differentiable_warping, module.py:78-84, at
     full size): loss, gradient norms and sliced gradients of tests/golden/train_cfg4_b2.npz"""
     from itermvs_amd import synthetic

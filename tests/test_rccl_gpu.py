@@ -50,14 +50,16 @@ def test_one_rank_nccl_process_group_runs_every_collective_of_the_path():
     assert skipped == 0 and n == 7 * 5 + 5 and same and ok_big and unused_none
 
 
-def test_bench_self_launch_under_torch_distributed_run_with_one_rank():
+def test_bench_self_launch_under_torch_distributed_run_with_one_rank(tmp_path):
     """`python bench.py --gpus N` re-executes itself as this command line; with N = 1 the launcher still sets
     TORCHELASTIC_RUN_ID, so shard.init_distributed() creates the nccl group and the timed region's barriers and
-    max-over-ranks all-reduce go through RCCL"""
+    max-over-ranks all-reduce go through RCCL.  The plain run's --dump-outputs writes the last step's two maps."""
     sys.path.insert(0, ROOT)
     import bench
+    import numpy as np
     cmd = bench.self_launch_command(1, ["--gpus", "1", "--steps", "2", "--warmup", "1", "--repeats", "1", "--minimal",
-                                        "--height", "128", "--width", "160", "--views", "3", "--iters", "2"])
+                                        "--height", "128", "--width", "160", "--views", "3", "--iters", "2",
+                                        "--dump-outputs", str(tmp_path)])
     assert cmd[1:3] == ["-m", "torch.distributed.run"] and "127.0.0.1" in cmd
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", ITERMVS_EXPECT_PROCESS_GROUP="nccl")
     env.pop("WORLD_SIZE", None)
@@ -66,6 +68,9 @@ def test_bench_self_launch_under_torch_distributed_run_with_one_rank():
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["value"] > 0 and line["steps"] == 2
     assert line["config"]["process_group"] == "nccl"
+    for name in ("depths_upsampled", "confidence_upsampled"):
+        a = np.load(tmp_path / f"{name}.npy")
+        assert a.shape == (1, 1, 128, 160) and a.dtype == np.float32 and np.isfinite(a).all(), name
 
 
 def test_bench_with_two_ranks_sharing_one_gpu_over_gloo():
@@ -74,7 +79,7 @@ def test_bench_with_two_ranks_sharing_one_gpu_over_gloo():
     torch.distributed.run share cuda:0, the process group is gloo (ITERMVS_DIST_BACKEND; RCCL wants a device per rank)"""
     sys.path.insert(0, ROOT)
     import bench
-    args = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "2", "--minimal",
+    args = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "2", "--full", "--minimal",
             "--height", "128", "--width", "160", "--views", "3", "--iters", "2"]
     cmd = bench.self_launch_command(2, args)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", ITERMVS_DIST_BACKEND="gloo")

@@ -3,7 +3,7 @@
 #     bash tools/gpu_session.sh <tag> <step> [<step> ...]
 # steps:  tests        full `pytest -m gpu`                               -> gpurun_out/<tag>_tests.log
 #         tests:<k>    `pytest -m gpu -k <k>` (use + for spaces)          -> gpurun_out/<tag>_tests_<n>.log
-#         bench        the default bench line                             -> gpurun_out/<tag>_bench.json
+#         bench        every leg of the bench (--full --repeats 9)        -> <tag>_bench.json
 #         bench:<args> bench.py with extra flags (use + for spaces)       -> gpurun_out/<tag>_bench_<n>.json
 #         trace        rocprofv3 --kernel-trace --stats of a minimal bench run + per-step timeline
 #         pmc          counter passes (tools/pmc_kernels.sh) + summary json
@@ -24,7 +24,7 @@ for step in "$@"; do
   case "$step" in
     tests)     timeout 1500 python -m pytest tests -m gpu -q -s --timeout 600 > ${O}_tests.log 2>&1; tail -3 ${O}_tests.log; grep -E "^FAILED|^ERROR" ${O}_tests.log | head -20 ;;
     tests:*)   timeout 1500 python -m pytest tests -m gpu -q -s --timeout 600 -k "$arg" > ${O}_tests_$n.log 2>&1; tail -3 ${O}_tests_$n.log; grep -E "^FAILED|^ERROR" ${O}_tests_$n.log | head -20 ;;
-    bench)     timeout 900 python bench.py > ${O}_bench.json 2> ${O}_bench.err; python tools/bench_digest.py ${O}_bench.json ;;
+    bench)     timeout 900 python bench.py --full --repeats 9 > ${O}_bench.json 2> ${O}_bench.err; python tools/bench_digest.py ${O}_bench.json ;;
     bench:*)   timeout 900 python bench.py $arg > ${O}_bench_$n.json 2> ${O}_bench_$n.err; python tools/bench_digest.py ${O}_bench_$n.json ;;
     trace)     (cd /tmp && export TMPDIR=/tmp && rm -rf $R/${O}_prof && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/${O}_prof -- python $R/bench.py --steps 30 --warmup 6 --repeats 1 --minimal > $R/${O}_prof.log 2>&1)
                python tools/step_timeline.py $(ls ${O}_prof/*/*kernel_trace.csv | head -1) > ${O}_timeline.txt 2>&1
