@@ -489,3 +489,75 @@ def test_rank_binds_to_the_cpus_of_its_gpus_numa_node(tmp_path):
     """)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "child ok" in r.stdout, r.stderr[-800:]
+
+
+def test_fp64_correlation_gradient_reference_matches_the_oracle_in_fp32():
+    """tests/corr_grad_reference.py (the float64 reference of the correlation backward tests) against autograd through
+    the oracle's own fp32 warp + group correlation + view-weighted mean, on a small case with two rigs, both branches"""
+    import corr_grad_reference as R
+    from itermvs_amd import synthetic
+    from oracle import itermvs_oracle as O
+    gen = torch.Generator().manual_seed(5)
+    b, v, h, w = 2, 4, 16, 24
+    sm = synthetic.make_sample(b, v, 4 * h, 4 * w, seed=3)
+    pr = [sm["proj_matrices"][f"level_{l}"] for l in (1, 2, 3)]
+    p12 = torch.stack([torch.stack([O.compose_projection(pr[i][:, s], pr[i][:, 0])[:, :3, :4].reshape(-1, 12)
+                                    for s in range(1, v)], 1) for i in range(3)])
+    sizes = {1: (2 * h, 2 * w), 2: (h, w), 3: (h // 2, w // 2)}
+    feats = {l: torch.randn((b * v, R.CHANS[l]) + sizes[l], generator=gen) for l in (1, 2, 3)}
+    ref_q = torch.randn((b, h, w, 96), generator=gen)
+    vw = torch.rand((b, v - 1, h, w), generator=gen)
+    inv_min, inv_max = torch.full((b, 1, 1, 1), 1 / 425.0), torch.full((b, 1, 1, 1), 1 / 935.0)
+    depth = O.iteration_depth_samples(torch.rand((b, 1, h, w), generator=gen), inv_min, inv_max)
+    gout = [torch.randn((b, n, 8, h, w), generator=gen) for n in (4, 4, 2)]
+
+    def rel(got, want):
+        return float((got.double() - want.double()).abs().max()) / max(1.0, float(want.abs().max()))
+
+    # iteration branch: the oracle's pieces in fp32, written out independently of the helper
+    fo = {l: feats[l].clone().requires_grad_(True) for l in (1, 2, 3)}
+    rq = ref_q.clone().requires_grad_(True)
+    loss, outs32 = 0, []
+    for i, l in enumerate((1, 2, 3)):
+        refl = rq[..., R.REF_Q_OFFSET[l]:R.REF_Q_OFFSET[l] + R.CHANS[l]].permute(0, 3, 1, 2)
+        pv = fo[l].view(b, v, *fo[l].shape[1:])
+        acc, wsum = 0, 1e-5
+        for s in range(1, v):
+            m = torch.cat([p12[i][:, s - 1].view(b, 3, 4), torch.zeros(b, 1, 4)], 1)
+            with torch.no_grad():
+                ix, iy, _ = O.warp_source_coords(m, depth[l], *sizes[l])
+            wv = vw[:, s - 1].view(b, 1, 1, h, w)
+            acc, wsum = acc + O.group_correlation(O.bilinear_gather(pv[:, s], ix, iy), refl) * wv, wsum + wv
+        outs32.append((acc / wsum).permute(0, 2, 1, 3, 4))
+        loss = loss + (outs32[-1] * gout[i]).sum()
+    loss.backward()
+    outs64 = R.iter_outputs(feats, ref_q, p12, vw, depth, b, v)
+    gf, grq = R.corr_iter_grads(feats, ref_q, p12, vw, depth, gout, b, v)
+    assert all(o.dtype == torch.float64 for o in outs64) and grq.dtype == torch.float64
+    for i, l in enumerate((1, 2, 3)):
+        assert rel(outs64[i], outs32[i].detach()) <= 2e-6, l
+        assert rel(gf[l], fo[l].grad) <= 2e-6, l
+        assert float(gf[l].view(b, v, -1)[:, 0].abs().max()) == 0.0 and float(gf[l].abs().max()) > 0.0
+    assert rel(grq, rq.grad) <= 2e-6
+    # in fp32 the helper IS the oracle's computation
+    gf32, grq32 = R.corr_iter_grads(feats, ref_q, p12, vw, depth, gout, b, v, dtype=torch.float32)
+    assert all(rel(gf32[l], fo[l].grad) <= 1e-6 for l in (1, 2, 3)) and rel(grq32, rq.grad) <= 1e-6
+
+    # initialisation branch: reference view gathered, sources scattered, 32 planes
+    h3, w3 = sizes[3]
+    f3 = feats[3].clone().requires_grad_(True)
+    d0 = O.initial_depth_samples(inv_min, inv_max, h3, w3)
+    g0 = torch.randn((b, v - 1, 32, 8, h3, w3), generator=gen)
+    pv = f3.view(b, v, *f3.shape[1:])
+    loss = 0
+    for s in range(1, v):
+        m = torch.cat([p12[2][:, s - 1].view(b, 3, 4), torch.zeros(b, 1, 4)], 1)
+        with torch.no_grad():
+            ix, iy, _ = O.warp_source_coords(m, d0, h3, w3)
+        loss = loss + (O.group_correlation(O.bilinear_gather(pv[:, s], ix, iy), pv[:, 0]).permute(0, 2, 1, 3, 4) * g0[:, s - 1]).sum()
+    loss.backward()
+    g3 = R.corr_init_grads(feats[3], p12[2], d0, g0, b, v)
+    assert g3.dtype == torch.float64 and rel(g3, f3.grad) <= 2e-6
+    assert float(g3.view(b, v, -1)[:, 0].abs().max()) > 0.0 and float(g3.view(b, v, -1)[:, 1:].abs().max()) > 0.0
+    err, scale = R.parity(g3.float(), g3)
+    assert err <= 1e-7 * scale

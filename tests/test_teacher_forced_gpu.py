@@ -207,16 +207,30 @@ def _oracle_corr_views(feat_pv, ref, p12_l, depth, size):
     return out
 
 
+class _LazyTraces(dict):
+    """storage name -> the traced oracle step with that feature storage, computed on first use (each storage's CPU oracle
+    step is paid by the first test that needs it, not all of them by the first test of the module)"""
+
+    def __init__(self, make):
+        super().__init__()
+        self._make = make
+
+    def __missing__(self, name):
+        self[name] = self._make(name)
+        return self[name]
+
+
 @pytest.fixture(scope="module")
 def cfg4_backward_trace():
     """one cfg-4 shaped training step of the CPU oracle at B = 2 (5 views, 640x512, 4 iterations, seed-0 weights, the batch
-    train.py --batch_size 2 builds), for fp32 and bf16 feature storage: traced tensors + the upstream gradients of every
-    Evaluation call (retain_grad on the aggregated correlations)"""
+    train.py --batch_size 2 builds), for fp32, bf16 and fp16 feature storage: traced tensors + the upstream gradients of
+    every Evaluation call (retain_grad on the aggregated correlations)"""
     from itermvs_amd import synthetic
     torch.set_num_threads(min(32, max(8, torch.get_num_threads())))
     imgs, projs, dmin, dmax, gt, mk = synthetic.make_training_batch(2, num_views=5, height=512, width=640, seed=2, hole_fraction=0.1)
-    out = {}
-    for name, storage in (("fp32", None), ("bf16", torch.bfloat16)):
+
+    def trace(name):
+        storage = STORAGE[name]
         w = {k: v.clone().requires_grad_(v.dtype.is_floating_point and "running" not in k) for k, v in load_weights("seed0").items()}
         tr = {}
         res = O.pipeline_forward(w, imgs, projs, dmin, dmax, iteration=4, test=False, training=True, trace=tr, feature_storage=storage)
@@ -224,18 +238,20 @@ def cfg4_backward_trace():
             for a in it["aggs"]:
                 a.retain_grad()
         O.full_loss(res["depths"], res["depths_upsampled"], res["confidences"], gt, mk, dmin, dmax, True).backward()
-        out[name] = dict(
+        return dict(
             feats={l: tr["feats_gathered"][l].detach() for l in (1, 2, 3)},
             view_w=tr["view_weights"].detach(),
             iters=[dict(nd_in=it["nd_in"].detach(), aggs=[a.detach() for a in it["aggs"]], up=[a.grad.detach() for a in it["aggs"]])
                    for it in tr["iters"]])
+
+    out = _LazyTraces(trace)
     p = torch.stack([projs[f"level_{l}"] for l in (1, 2, 3)])
     p12 = torch.stack([torch.stack([O.compose_projection(p[i][:, s], p[i][:, 0])[:, :3, :4].reshape(-1, 12) for s in range(1, 5)], 1)
                        for i in range(3)])
     return out, p12, (1.0 / dmin), (1.0 / dmax)
 
 
-@pytest.mark.parametrize("storage", ["fp32", "bf16"])
+@pytest.mark.parametrize("storage", ["fp32", "bf16", "fp16"])
 @pytest.mark.parametrize("it", [0, 2])
 def test_corr_iter_backward_on_the_oracles_training_tensors(cfg4_backward_trace, storage, it):
     """itermvs_corr_iter_backward at 640x512, B = 2, 4 source views: dL/dsrc (scatter) and dL/dref_q (gather) for the
@@ -267,9 +283,9 @@ def test_corr_iter_backward_on_the_oracles_training_tensors(cfg4_backward_trace,
     loss.backward()
     dev = lambda x: x.to("cuda")
     fg = {l: dev(t["feats"][l]).contiguous(memory_format=torch.channels_last).requires_grad_(True) for l in (1, 2, 3)}
-    stored = None if storage == "fp32" else {l: fg[l].detach().to(torch.bfloat16) for l in fg}
+    stored = None if storage == "fp32" else {l: fg[l].detach().to(STORAGE[storage]) for l in fg}
     if stored is not None:
-        assert all(torch.equal(stored[l].float(), fg[l].detach()) for l in fg)                   # the oracle's storage model == bf16 values
+        assert all(torch.equal(stored[l].float(), fg[l].detach()) for l in fg)                   # the oracle's storage model == 16-bit values
     rqd = dev(ref_q.detach()).requires_grad_(True)
     outs = ops.corr_iter_train(fg, b, v, rqd, dev(p12), dev(vw), dev(inv_min), dev(inv_max), dev(nd), sample_offsets(), stored=stored)
     worst = 0.0
@@ -291,7 +307,7 @@ def test_corr_iter_backward_on_the_oracles_training_tensors(cfg4_backward_trace,
     print(f"teacher-forced backward, iteration {it}, {storage}: forward {worst:.1e}, gradients (max abs / scale) {rep}")
 
 
-@pytest.mark.parametrize("storage", ["fp32", "bf16"])
+@pytest.mark.parametrize("storage", ["fp32", "bf16", "fp16"])
 def test_corr_init_backward_on_the_oracles_training_features(cfg4_backward_trace, storage):
     """itermvs_corr_init_backward at the cfg-4 size (level 3: 64x80, 32 planes, B = 2, 4 source views) on the oracle's
     FeatureNet output; upstream gradient: seeded noise (the per-view volumes are not a traced seam of the oracle)"""
@@ -306,7 +322,8 @@ def test_corr_init_backward_on_the_oracles_training_features(cfg4_backward_trace
     corrs = _oracle_corr_views(pv, pv[:, 0], p12[2], depth, (h3, w3))
     sum((c.permute(0, 2, 1, 3, 4) * gw[:, s]).sum() for s, c in enumerate(corrs)).backward()
     fg = f3.detach().to("cuda").contiguous(memory_format=torch.channels_last).requires_grad_(True)
-    stored = None if storage == "fp32" else fg.detach().to(torch.bfloat16)
+    stored = None if storage == "fp32" else fg.detach().to(STORAGE[storage])
+    assert stored is None or torch.equal(stored.float(), fg.detach())
     out = ops.corr_init_train(fg, b, v, p12[2].to("cuda"), inv_min.to("cuda"), inv_max.to("cuda"), 32, stored=stored)
     want = torch.stack([c.detach().permute(0, 2, 1, 3, 4) for c in corrs], 1)
     assert float((out.detach().cpu() - want).abs().max()) <= 5e-5 * max(1.0, float(want.abs().max()))
