@@ -175,6 +175,24 @@ def make_scene_sample(num_views: int = 5, height: int = 512, width: int = 640, s
     }
 
 
+def make_scene_batch(num_views: int = 5, height: int = 512, width: int = 640, seeds=(0, 1), depth_ranges=None) -> Dict[str, object]:
+    """A batch of :func:`make_scene_sample` scenes, item ``i`` seeded ``seeds[i]`` (its own rig and texture), concatenated
+    along dim 0 in the sample-dict schema.  ``depth_ranges``: optional ``(depth_min, depth_max)`` per item (default: the
+    DTU range for every item)."""
+    parts = [make_scene_sample(num_views=num_views, height=height, width=width, seed=s) for s in seeds]
+    cat = lambda pick: torch.cat([pick(p) for p in parts], 0)  # noqa: E731
+    out = {"imgs": {k: cat(lambda p: p["imgs"][k]) for k in parts[0]["imgs"]},
+           "proj_matrices": {k: cat(lambda p: p["proj_matrices"][k]) for k in parts[0]["proj_matrices"]},
+           "depth_min": cat(lambda p: p["depth_min"]), "depth_max": cat(lambda p: p["depth_max"]),
+           "depth_gt": cat(lambda p: p["depth_gt"])}
+    if depth_ranges is not None:
+        if len(depth_ranges) != len(seeds):
+            raise ValueError("one depth range per item")
+        out["depth_min"] = torch.tensor([float(r[0]) for r in depth_ranges], dtype=torch.float32)
+        out["depth_max"] = torch.tensor([float(r[1]) for r in depth_ranges], dtype=torch.float32)
+    return out
+
+
 def make_training_sample(num_views: int = 5, height: int = 512, width: int = 640, seed: int = 2, hole_fraction: float = 0.1):
     """One BASELINE cfg-4 shaped training sample (B = 1): the photo-consistent scene of :func:`make_scene_sample` with its
     exact depth as ground truth and a seeded validity mask with ``hole_fraction`` of the pixels masked out, in the

@@ -85,8 +85,34 @@ def _rates(a, b):
     return float((rel > 1e-4).float().mean()), float(rel.median()), float(rel.max())
 
 
-@pytest.mark.parametrize("tag", ["seed0", "dtu_scene", "dtu"])
-def test_cfg1_against_reference_outputs(tag):
+ARITHMETIC = ("bf16x3", "fp32")
+_CFG1 = {}
+
+
+def _cfg1_oracles(tag):
+    """(sample, CPU oracle trace + outputs, PyTorch-ROCm oracle trace + outputs) of a cfg-1 case: they do not depend on the
+    engine's arithmetic, so the last case's are kept for the next item (the two arithmetics of a case run back to back)"""
+    if tag not in _CFG1:
+        _CFG1.clear()
+        from itermvs_amd import synthetic
+        from oracle import itermvs_oracle as O
+        w = load_weights(tag.split("_")[0])
+        if tag.endswith("scene"):
+            s = synthetic.make_scene_sample(num_views=5, height=512, width=640, seed=0)
+        else:
+            s = synthetic.make_sample(batch=1, num_views=5, height=512, width=640, seed=0)
+        imgs, pm, dmin, dmax = to_dev(s)
+        t_cpu, t_gpu = {}, {}
+        with torch.no_grad():
+            o_cpu = O.pipeline_forward(w, s["imgs"], s["proj_matrices"], s["depth_min"], s["depth_max"], 4, trace=t_cpu)
+            o_gpu = O.pipeline_forward({k: v.to(DEV) for k, v in w.items()}, imgs, pm, dmin, dmax, 4, trace=t_gpu)
+        _CFG1[tag] = (s, t_cpu, o_cpu, t_gpu, o_gpu)
+    return _CFG1[tag]
+
+
+@pytest.mark.parametrize("tag,arithmetic", [pytest.param(t, a, id=t if a == "bf16x3" else f"{t}-fp32")
+                                            for t in ("seed0", "dtu_scene", "dtu") for a in ARITHMETIC])
+def test_cfg1_against_reference_outputs(tag, arithmetic):
     """BASELINE cfg 1/2: V=5, 640x512, 4 iterations, seeded inputs regenerated here.
 
     End-to-end the network is chaotic: one arg-max flip (from a 1e-7 rounding difference between
@@ -98,30 +124,25 @@ def test_cfg1_against_reference_outputs(tag):
       (2) the engine's mismatch rate against the CPU oracle / the reference golden is no worse
           than the platform floor = the SAME oracle code run with stock PyTorch-ROCm ops here;
       (3) with benign weights (seed0) engine and PyTorch-ROCm oracle agree at EVERY pixel.
+    Both convolution arithmetics (``Pipeline.conv_arithmetic``) pass the same gates.
     Kernel-level parity on identical inputs is asserted in test_kernels_gpu.py."""
-    from itermvs_amd import synthetic
     from itermvs_amd.engine import InferenceEngine
-    from oracle import itermvs_oracle as O
     torch.set_num_threads(min(16, torch.get_num_threads()))
     g = golden(f"cfg1_{tag}.npz")
     wtag = tag.split("_")[0]
-    w = load_weights(wtag)
-    if tag.endswith("scene"):
-        s = synthetic.make_scene_sample(num_views=5, height=512, width=640, seed=0)
-    else:
-        s = synthetic.make_sample(batch=1, num_views=5, height=512, width=640, seed=0)
+    s, t_cpu, o_cpu, t_gpu, o_gpu = _cfg1_oracles(tag)
     model = make_model(wtag, 4)
+    model.conv_arithmetic = arithmetic
     out = model(*to_dev(s))                                                         # public API (net.py:78)
+    assert model._engine.split3 == (arithmetic == "bf16x3")
     assert set(out.keys()) == {"depths_upsampled", "confidence_upsampled"}          # net.py:125-128
     d, c = out["depths_upsampled"], out["confidence_upsampled"]
     assert d.shape == (1, 1, 512, 640) and c.shape == (1, 1, 512, 640)
 
-    t_cpu, t_gpu, t_eng = {}, {}, {}
+    t_eng = {}
     imgs, pm, dmin, dmax = to_dev(s)
     with torch.no_grad():
-        o_cpu = O.pipeline_forward(w, s["imgs"], s["proj_matrices"], s["depth_min"], s["depth_max"], 4, trace=t_cpu)
-        o_gpu = O.pipeline_forward({k: v.to(DEV) for k, v in w.items()}, imgs, pm, dmin, dmax, 4, trace=t_gpu)
-        eng = InferenceEngine(model.weights(), 4)
+        eng = InferenceEngine(model.weights(), 4, conv_arithmetic=arithmetic)
         pj = {l: pm[f"level_{l}"] for l in (1, 2, 3)}
         d3, _ = eng.run(imgs["level_0"], pj, dmin, dmax)
         d2, _ = eng.run(imgs["level_0"], pj, dmin, dmax, trace=t_eng)
@@ -141,7 +162,7 @@ def test_cfg1_against_reference_outputs(tag):
     bad_cpu, med_cpu, max_cpu = _rates(d, o_cpu["depths_upsampled"])
     bad_gold, med_gold, _ = _rates(d[:, :, ::4, ::4], g["depth_sub"])
     bad_gpu, med_gpu, max_gpu = _rates(d, o_gpu["depths_upsampled"])
-    print(f"cfg1 {tag}: engine-vs-oracleCPU {bad_cpu:.4f} (median {med_cpu:.1e}) | engine-vs-golden {bad_gold:.4f} | "
+    print(f"cfg1 {tag} {arithmetic}: engine-vs-oracleCPU {bad_cpu:.4f} (median {med_cpu:.1e}) | engine-vs-golden {bad_gold:.4f} | "
           f"engine-vs-oracleROCm {bad_gpu:.4f} (max {max_gpu:.1e}) | floors: ROCm-vs-CPU {floor:.4f}, "
           f"CPU(EPYC)-vs-golden(Xeon) {host_floor:.4f} | first-argmax flips {flips0:.5f} (floor {floor0:.5f})")
     med_lim = 1e-4 if tag == "dtu" else 2e-6
@@ -171,18 +192,46 @@ def test_cfg1_against_reference_outputs(tag):
 
 
 def test_batch_of_two_equals_two_singles():
+    """a batch item's outputs do not depend on its batch-mate: bit for bit the item run alone, in both convolution
+    arithmetics, with a different rig and depth range per item (per-item strides, inv_min / inv_max and projections,
+    the packed CorrNet scores and the reference-view gather of the up-sampling head at B > 1)"""
     from itermvs_amd import synthetic
-    model = make_model("seed0", 2)
     s2 = synthetic.make_sample(batch=2, num_views=3, height=64, width=96, seed=2)
-    out2 = model(*to_dev(s2))
-    for b in range(2):
-        s1 = {"imgs": {k: v[b:b + 1] for k, v in s2["imgs"].items()},
-              "proj_matrices": {k: v[b:b + 1] for k, v in s2["proj_matrices"].items()},
-              "depth_min": s2["depth_min"][b:b + 1], "depth_max": s2["depth_max"][b:b + 1]}
-        out1 = model(*to_dev(s1))
-        rel = (out2["depths_upsampled"][b] - out1["depths_upsampled"][0]).abs() / out1["depths_upsampled"][0]
-        assert float((rel > 1e-4).float().mean()) <= 0.02
-        assert float(rel.median()) <= 1e-6
+    s2["depth_min"][1], s2["depth_max"][1] = 380.0, 1000.0
+    for arithmetic in ARITHMETIC:
+        model = make_model("seed0", 2)
+        model.conv_arithmetic = arithmetic
+        out2 = model(*to_dev(s2))
+        for b in range(2):
+            s1 = {"imgs": {k: v[b:b + 1] for k, v in s2["imgs"].items()},
+                  "proj_matrices": {k: v[b:b + 1] for k, v in s2["proj_matrices"].items()},
+                  "depth_min": s2["depth_min"][b:b + 1], "depth_max": s2["depth_max"][b:b + 1]}
+            out1 = model(*to_dev(s1))
+            rel = (out2["depths_upsampled"][b] - out1["depths_upsampled"][0]).abs() / out1["depths_upsampled"][0]
+            assert float((rel > 1e-4).float().mean()) <= 0.02
+            assert float(rel.median()) <= 1e-6
+            assert torch.equal(out2["depths_upsampled"][b], out1["depths_upsampled"][0]), (arithmetic, b, float(rel.max()))
+            assert torch.equal(out2["confidence_upsampled"][b], out1["confidence_upsampled"][0]), (arithmetic, b)
+
+
+@pytest.mark.parametrize("batch", [1, 2])
+def test_side_branch_equals_the_default_run(batch):
+    """``side_branch=True`` (ref_quarter and the up-sampling weights on a second stream, eager) computes what the default
+    run computes, bit for bit, in both convolution arithmetics"""
+    from itermvs_amd import synthetic
+    from itermvs_amd.engine import InferenceEngine
+    s = synthetic.make_sample(batch=batch, num_views=4, height=64, width=96, seed=6)
+    imgs, pm, dmin, dmax = to_dev(s)
+    pj = {l: pm[f"level_{l}"] for l in (1, 2, 3)}
+    w = make_model("seed0", 2).weights()
+    for arithmetic in ARITHMETIC:
+        with torch.no_grad():
+            d0, c0 = (x.clone() for x in InferenceEngine(w, 2, conv_arithmetic=arithmetic).run(imgs["level_0"], pj, dmin, dmax))
+            side = InferenceEngine(w, 2, conv_arithmetic=arithmetic, side_branch=True)
+            d1, c1 = side.run(imgs["level_0"], pj, dmin, dmax)
+            torch.cuda.synchronize()
+        assert side._side is not None                                   # the second stream was used
+        assert torch.equal(d0, d1) and torch.equal(c0, c1), arithmetic
 
 
 def test_views_and_iterations_are_runtime_parameters():
@@ -260,19 +309,31 @@ def test_16bit_feature_storage_end_to_end(fdt):
     assert abs(e16 - e32) <= 0.1 and e16 < 1.0               # reconstructs the plane as well as fp32 does
 
 
-def test_graph_replay_equals_eager():
-    """hipGraph segments + eager corr_iter launches reproduce the eager engine bit for bit, for changing inputs."""
+def _graph_replay_equals_eager(arithmetic, batch):
     from itermvs_amd import synthetic
     model = make_model("seed0", 3)
     graphed = make_model("seed0", 3)
+    model.conv_arithmetic = graphed.conv_arithmetic = arithmetic
     graphed.use_graphs = True
     for seed in (1, 2, 3):
-        s = synthetic.make_sample(batch=1, num_views=4, height=64, width=96, seed=seed)
+        s = synthetic.make_sample(batch=batch, num_views=4, height=64, width=96, seed=seed)
         a = model(*to_dev(s))
         b = graphed(*to_dev(s))
         torch.cuda.synchronize()
         assert torch.equal(a["depths_upsampled"], b["depths_upsampled"])
         assert torch.equal(a["confidence_upsampled"], b["confidence_upsampled"])
+    assert len(graphed._runners) == 1 and graphed._engine.split3 == (arithmetic == "bf16x3")
+
+
+def test_graph_replay_equals_eager():
+    """hipGraph segments + eager corr_iter launches reproduce the eager engine bit for bit, for changing inputs."""
+    _graph_replay_equals_eager("bf16x3", 1)
+
+
+@pytest.mark.parametrize("arithmetic,batch", [("fp32", 1), ("bf16x3", 2), ("fp32", 2)])
+def test_graph_replay_equals_eager_other_routes(arithmetic, batch):
+    """the same for the fp32 convolution arithmetic and for a batch of two"""
+    _graph_replay_equals_eager(arithmetic, batch)
 
 
 def test_smoke_entry():
