@@ -32,18 +32,22 @@ class CapturedTrainStep:
     caching allocator and Adam's state settle); the next call captures the graph with that batch as the static inputs and
     replays it; later calls copy their batch into the static buffers and replay.  ``batch`` = (imgs, proj_matrices,
     depth_min, depth_max, depth_gt, mask) like ``train.synthetic_batch`` / the reference's collated sample, always of the
-    same shapes.  The optimizer must be created with ``capturable=True`` (its step counter lives on the device); learning
-    rate schedules keep working when the rate is a device tensor (``lr=torch.tensor(...)``), which torch's schedulers fill
-    in place.  ``check()`` raises the deferred NaN assert of module.py:83,87 (one 4-byte read-back); the flagged step itself
-    was a no-op on the weights (see ``_step``).  The flag is shared with every forward of the model: call ``check()`` after
-    validation forwards too, so a bad validation sample is not attributed to the next training step."""
+    same shapes.  The optimizer must be created with ``capturable=True`` (its step counter lives on the device) and with
+    its learning rate in a device tensor (``lr=torch.tensor(..., device=...)``), which torch's schedulers fill in place.
+    ``check()`` raises the deferred NaN assert of module.py:83,87 (one 4-byte read-back) and clears the flag.  A flagged step
+    is a no-op on the weights (see ``_step``): every parameter keeps its bits, Adam's moments decay by their betas and stay
+    finite, and Adam's step counter still advances by one; with several ranks the flag is reduced with the gradients, so
+    every rank skips the step and every rank's ``check()`` raises.  The model can still be saved or resumed.  The flag is
+    shared with every forward of the model: call ``check()`` after validation forwards too, so a bad validation sample is
+    not attributed to the next training step."""
 
     def __init__(self, model, optimizer, regress: bool, clip: float = 2.0, warmup: int = 3):
         if not all(g.get("capturable", False) for g in optimizer.param_groups):
             raise ValueError("CapturedTrainStep needs an optimizer created with capturable=True")
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and dist.get_backend() != "nccl":
-            raise ValueError("CapturedTrainStep: the gradient all-reduce is captured with the step and needs the RCCL (nccl) backend")
+        # a flagged step is skipped by setting the rate to 0 for that step: a float rate would be baked into the graph, and
+        # Adam would still move the parameters by their momentum
+        if not all(torch.is_tensor(g["lr"]) and g["lr"].is_cuda for g in optimizer.param_groups):
+            raise ValueError("CapturedTrainStep needs the learning rate in a device tensor (lr=torch.tensor(..., device=...))")
         self.model, self.opt, self.regress, self.clip = model, optimizer, regress, clip
         self.warmup = warmup
         self.calls = 0
@@ -63,7 +67,9 @@ class CapturedTrainStep:
         out = self.model(imgs, projs, dmin, dmax)
         loss = full_loss(out["depths"], out["depths_upsampled"], out["confidences"], gt, mask, dmin, dmax, self.regress)
         loss.backward()
-        ddp.flat_allreduce_gradients(self.params)
+        # the flag rides in the gradient bucket: after this every rank holds the same gradients AND the same flag (the OR
+        # over the ranks), so every rank skips a step that any rank flagged
+        ddp.flat_allreduce_gradients(self.params, flag=self.nan_flag)
         torch.nn.utils.clip_grad_norm_(self.params, self.clip)
         # The reference asserts on a NaN projection BEFORE any update (module.py:83,87); here the assert is deferred to
         # ``check()``, so a flagged step must leave the weights alone: its (NaN) gradients are replaced by zeros and the
@@ -74,7 +80,7 @@ class CapturedTrainStep:
         for p in self.params:
             if p.grad is not None:
                 p.grad = torch.where(ok, p.grad, zero)
-        rates = [(g, g["lr"].clone()) for g in self.opt.param_groups if torch.is_tensor(g["lr"])]
+        rates = [(g, g["lr"].clone()) for g in self.opt.param_groups]
         for g, _ in rates:
             g["lr"].mul_(ok.to(g["lr"].dtype).reshape(g["lr"].shape))
         self.opt.step()
@@ -93,6 +99,10 @@ class CapturedTrainStep:
             cur.wait_stream(self.stream)
             return out
         if self.graph is None:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and dist.get_backend() != "nccl":
+                raise ValueError("CapturedTrainStep: the gradient all-reduce is captured with the step and needs the RCCL (nccl) "
+                                 "backend (the eager warm-up steps run under any backend)")
             self.static = tuple({k: v.clone() for k, v in part.items()} if isinstance(part, dict) else part.clone() for part in batch)
             self.stream.wait_stream(cur)
             with torch.cuda.stream(self.stream):

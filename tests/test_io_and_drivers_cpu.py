@@ -151,6 +151,35 @@ def test_flat_gradient_allreduce_two_ranks():
     assert res[0][4] == res[1][4] == 5 * 3 + 3 and res[0][5] is None             # one bucket, unused parameter skipped
 
 
+def _flag_worker(rank, world, port, q):
+    os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
+                      MASTER_PORT=str(port))
+    from itermvs_amd import ddp, shard
+    shard.init_distributed(backend="gloo")
+    lin = torch.nn.Linear(5, 3)
+    ddp.broadcast_parameters(lin)
+    seen = []
+    for flagged_rank in (None, 1, 0):                   # no rank, rank 1, rank 0 raises its flag
+        lin.zero_grad(set_to_none=False)
+        lin(torch.full((2, 5), float(rank + 1))).sum().backward()
+        flag = torch.tensor([1 if rank == flagged_rank else 0], dtype=torch.int32)
+        n = ddp.flat_allreduce_gradients(lin.parameters(), flag=flag)
+        seen.append((int(flag.item()), flag.dtype, n, lin.weight.grad.numpy().copy()))
+    q.put((rank, seen))
+    torch.distributed.destroy_process_group()
+
+
+def test_flat_gradient_allreduce_carries_the_flag_to_every_rank():
+    """CapturedTrainStep's NaN-projection flag rides in the gradient bucket: after the all-reduce every rank holds 1 when any
+    rank raised it (and 0 when none did), the flag keeps its dtype, and the gradients are averaged as without it"""
+    from conftest import run_ranks
+    (_, s0), (_, s1) = run_ranks(_flag_worker, 2)
+    for (f0, d0, n0, g0), (f1, d1, n1, g1), want in zip(s0, s1, (0, 1, 1)):
+        assert f0 == f1 == want and d0 == d1 == torch.int32
+        assert n0 == n1 == 5 * 3 + 3                                     # the flag element is not counted as a gradient
+        assert np.array_equal(g0, g1) and np.allclose(g0, np.full((3, 5), 1.5 * 2))   # mean of 2 * 1 and 2 * 2
+
+
 def test_synthetic_batch_seeds_stay_in_range_for_validation_steps_at_scale():
     """train.py's validation uses steps from 10_000_019 on: with train_dtu.sh's --batch_size 4, or 8 ranks, the scene seed
     used to exceed numpy's 2**32 limit and crash at the end of epoch 0"""

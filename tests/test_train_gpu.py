@@ -1,5 +1,8 @@
 """Training form of the pipeline on the MI355X (HIP warp forward/backward inside autograd) vs
 the reference's forward + full_loss + backward captured in tests/golden/train_small.npz."""
+import math
+
+import numpy as np
 import pytest
 import torch
 
@@ -397,3 +400,195 @@ def test_resume_across_launch_modes(tmp_path):
     assert isinstance(g3["lr"], float) and abs(g3["lr"] - 5e-6) < 1e-10 and g3["capturable"] is False
     loss, _ = T.train_step(m3, opt3, batches[0], True)
     assert loss == loss and {float(st["step"]) for st in opt3.state.values()} == {6.0}
+
+
+# ---- the deferred NaN-projection assert of the captured step (module.py:83,87) ----------------------------------------------
+def _flag_batches(seeds, bad):
+    """96x128, B = 2, 3-view training batches; ``bad[i]``: None, "singular" (item 0's reference camera zeroed at every level)
+    or "src_nan" (one NaN in source view 2 of item 1 at every level)"""
+    from itermvs_amd import synthetic
+    to = lambda d: {k: v.to(DEV) for k, v in d.items()}  # noqa: E731
+    out = []
+    for seed, kind in zip(seeds, bad):
+        imgs, projs, dmin, dmax, gt, mask = synthetic.make_training_batch(2, num_views=3, height=96, width=128, seed=seed, hole_fraction=0.1)
+        projs = {k: v.clone() for k, v in projs.items()}
+        for k in projs:
+            if kind == "singular":
+                projs[k][0, 0] = 0.0
+            elif kind == "src_nan":
+                projs[k][1, 2, 1, 2] = float("nan")
+        out.append((to(imgs), to(projs), dmin.to(DEV), dmax.to(DEV), to(gt), to(mask)))
+    return out
+
+
+def _fresh_model(iteration=2):
+    from itermvs_amd.net import Pipeline
+    m = Pipeline(iteration=iteration, test=False)
+    m.load_state_dict(load_weights("seed0"))
+    return m.to(DEV).train()
+
+
+def _adam(model, lr=1e-5, weight_decay=0.0):
+    return torch.optim.Adam(model.parameters(), lr=torch.tensor(lr, device=DEV), betas=(0.9, 0.999), weight_decay=weight_decay,
+                            capturable=True)
+
+
+def _adam_state(opt):
+    return {id(p): {k: v.detach().clone() for k, v in st.items()} for p, st in opt.state.items()}
+
+
+def _assert_flagged_step_kept_the_weights(model, opt, before, state_before):
+    """a flagged step: every parameter keeps its bits; Adam's moments are finite and decayed by their betas (a zero
+    gradient), its step counter advanced by one"""
+    for (name, p), q in zip(model.named_parameters(), before):
+        assert torch.equal(p.detach(), q), name
+    for p, st in opt.state.items():
+        old = state_before[id(p)]
+        assert bool(torch.isfinite(st["exp_avg"]).all()) and bool(torch.isfinite(st["exp_avg_sq"]).all())
+        wd = opt.param_groups[0]["weight_decay"]
+        if wd == 0:
+            assert torch.allclose(st["exp_avg"], 0.9 * old["exp_avg"], rtol=1e-6, atol=0)
+            assert torch.allclose(st["exp_avg_sq"], 0.999 * old["exp_avg_sq"], rtol=1e-6, atol=0)
+        assert float(st["step"]) == float(old["step"]) + 1
+
+
+@pytest.mark.parametrize("eager_bad,replay_bad", [("singular", "src_nan"), ("src_nan", "singular")])
+def test_captured_step_skips_a_flagged_step(eager_bad, replay_bad, tmp_path):
+    """CapturedTrainStep with a bad camera in one eager warm-up batch and in one replayed batch (96x128, B = 2, 3 views, like
+    test_captured_training_step_equals_the_eager_step): across each flagged step every parameter keeps its bits and Adam's state
+    stays finite; ``check()`` raises once and clears the flag; the next clean step gives a finite loss and moves the parameters
+    by about lr.  A checkpoint written after the replayed flagged step and resumed (train.restore_optimizer_mode) gives the
+    uninterrupted run's next loss."""
+    import train as T
+    from itermvs_amd.train_step import CapturedTrainStep
+    lr = 1e-5
+    kinds = [None, eager_bad, None, None, replay_bad, None]         # warm-up 3: steps 0-2 eager, 3 captures, 4-5 replay
+    batches = _flag_batches([5 * i + 1 for i in range(6)], kinds)
+    model = _fresh_model()
+    opt = _adam(model, lr)
+    cap = CapturedTrainStep(model, opt, regress=True, clip=2.0, warmup=3)
+    losses = []
+    for i, (bt, kind) in enumerate(zip(batches, kinds)):
+        before = [p.detach().clone() for p in model.parameters()]
+        state = _adam_state(opt)
+        loss, err = cap.step(bt)
+        torch.cuda.synchronize()
+        losses.append(float(loss))
+        if kind is None:
+            cap.check()
+            assert math.isfinite(losses[-1]) and math.isfinite(float(err)), (i, losses)
+            moved = max(float((p.detach() - q).abs().max()) for p, q in zip(model.parameters(), before))
+            assert 0.5 * lr <= moved <= 2.0 * lr, (i, moved)               # Adam moves ~lr per step
+        else:
+            _assert_flagged_step_kept_the_weights(model, opt, before, state)
+            with pytest.raises(AssertionError, match="nan in proj"):
+                cap.check()
+            assert int(cap.nan_flag.item()) == 0
+            cap.check()                                                   # raised once, then cleared
+        if i == 4:
+            assert cap.graph is not None
+            T.save_checkpoint(str(tmp_path / "model_000000.ckpt"), 0, model, opt)
+    assert cap.graph is not None and cap.calls == 6
+    assert {float(st["step"]) for st in opt.state.values()} == {6.0}     # the two flagged steps are counted
+
+    # resume from the checkpoint written after the replayed flagged step: the same next-step loss
+    state = torch.load(str(tmp_path / "model_000000.ckpt"), map_location="cpu", weights_only=False)
+    assert all(bool(torch.isfinite(v).all()) for v in state["model"].values() if v.is_floating_point())
+    m2 = _fresh_model()
+    m2.load_checkpoint_state(state["model"], strict=False)
+    opt2 = _adam(m2, lr)
+    opt2.load_state_dict(state["optimizer"])
+    T.restore_optimizer_mode(opt2, True, DEV)
+    cap2 = CapturedTrainStep(m2, opt2, regress=True, clip=2.0, warmup=1)
+    loss2 = float(cap2.step(batches[5])[0])
+    cap2.check()
+    assert abs(loss2 - losses[5]) <= 1e-5 * abs(losses[5]), (loss2, losses[5])
+
+
+def test_captured_step_with_weight_decay_skips_a_flagged_step():
+    """train.py --graph --wd: Adam adds wd * p to the (zeroed) gradient, so a flagged step still feeds the moments -- the rate
+    gate alone keeps the parameters: bit-identical across an eager and a replayed flagged step"""
+    from itermvs_amd.train_step import CapturedTrainStep
+    kinds = ["singular", None, "src_nan", None]                     # warm-up 1: step 0 eager, 1 captures, 2-3 replay
+    batches = _flag_batches([3, 13, 23, 33], kinds)
+    model = _fresh_model()
+    opt = _adam(model, 1e-5, weight_decay=1e-2)
+    cap = CapturedTrainStep(model, opt, regress=True, clip=2.0, warmup=1)
+    for bt, kind in zip(batches, kinds):
+        before = [p.detach().clone() for p in model.parameters()]
+        state = _adam_state(opt)
+        loss = float(cap.step(bt)[0])
+        torch.cuda.synchronize()
+        if kind is None:
+            cap.check()
+            assert math.isfinite(loss)
+            assert any(not torch.equal(p.detach(), q) for p, q in zip(model.parameters(), before))
+        else:
+            if state:
+                _assert_flagged_step_kept_the_weights(model, opt, before, state)
+            for (name, p), q in zip(model.named_parameters(), before):
+                assert torch.equal(p.detach(), q), name
+            with pytest.raises(AssertionError, match="nan in proj"):
+                cap.check()
+    assert cap.graph is not None
+
+
+def test_captured_step_refuses_a_rate_that_is_not_a_device_tensor():
+    """a flagged step is skipped by zeroing that step's rate in place: a Python float (or a host tensor) cannot be gated inside
+    the graph, and Adam would move the parameters by its momentum -- refused at construction"""
+    from itermvs_amd.train_step import CapturedTrainStep
+    model = _fresh_model(1)
+    for lr in (1e-3, torch.tensor(1e-3)):
+        with pytest.raises(ValueError, match="learning rate"):
+            CapturedTrainStep(model, torch.optim.Adam(model.parameters(), lr=lr, capturable=True), regress=True)
+    CapturedTrainStep(model, _adam(model), regress=True)
+
+
+def _flag_ddp_worker(rank, world, port, q):
+    """one rank of a CapturedTrainStep run under gloo on the shared cuda:0 (eager steps only: warm-up never ends); rank 1's
+    second batch has a singular reference camera"""
+    import os
+    import torch.distributed as dist
+    from itermvs_amd import ddp
+    from itermvs_amd.train_step import CapturedTrainStep
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    torch.cuda.set_device(0)
+    model = _fresh_model()
+    ddp.broadcast_parameters(model)
+    cap = CapturedTrainStep(model, _adam(model), regress=True, clip=2.0, warmup=100)
+    batches = _flag_batches([100 * rank + s for s in (1, 2, 3)], [None, "singular" if rank == 1 else None, None])
+    snap = lambda: [p.detach().cpu().numpy().copy() for p in model.parameters()]  # noqa: E731
+    raised, losses, params = [], [], []
+    for bt in batches:
+        params.append(snap())
+        losses.append(float(cap.step(bt)[0]))
+        try:
+            cap.check()
+            raised.append(False)
+        except AssertionError:
+            raised.append(True)
+    params.append(snap())
+    steps = sorted({float(st["step"]) for st in cap.opt.state.values()})
+    q.put((rank, raised, losses, params, steps, cap.graph is None))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_two_ranks_both_skip_a_step_one_rank_flagged():
+    """two processes share cuda:0 under gloo, each runs CapturedTrainStep eagerly on rank-local batches; rank 1's camera is
+    singular on step 2.  The flag is reduced with the gradients: on BOTH ranks the parameters after that step are bit-identical
+    to each other and to their values before it, and ``check()`` raises on both; the clean step after keeps both ranks identical
+    and finite."""
+    (_, raised0, loss0, p0, steps0, eager0), (_, raised1, loss1, p1, steps1, eager1) = run_ranks(_flag_ddp_worker, 2, timeout=600,
+                                                                                                attempts=1)
+    assert eager0 and eager1
+    assert raised0 == raised1 == [False, True, False]
+    assert steps0 == steps1 == [3.0]
+    for k in range(4):                                                # both ranks hold the same weights throughout
+        assert all(np.array_equal(a, b) for a, b in zip(p0[k], p1[k])), k
+    assert any(not np.array_equal(a, b) for a, b in zip(p0[0], p0[1]))     # step 1 moved them
+    assert all(np.array_equal(a, b) for a, b in zip(p0[1], p0[2]))         # step 2 (flagged on rank 1 only) did not
+    assert any(not np.array_equal(a, b) for a, b in zip(p0[2], p0[3]))     # step 3 did
+    assert all(np.isfinite(a).all() for a in p0[3])
+    assert all(math.isfinite(x) for x in loss0 + loss1)
