@@ -63,6 +63,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--no_graphs", action="store_true",
                    help="launch every kernel from Python (~85 launches per depth map) instead of replaying one hipGraph per depth map "
                         "(captured once per image shape; results are bit-identical)")
+    p.add_argument("--feature_cache", type=int, default=0,
+                   help="--dataset folder only: keep the feature pyramids of at most N images on the GPU and compute each image's "
+                        "pyramid once while it stays cached, instead of once per depth map that reads it (scan mode, "
+                        "itermvs_amd.scan_cache; ranks then take contiguous blocks of (scan, view)).  0 = off (default); "
+                        "N must be >= n_views.  The PFMs are byte-identical to the run without it")
     p.add_argument("--geo_pixel_thres", type=float, default=1)
     p.add_argument("--geo_depth_thres", type=float, default=0.01)
     p.add_argument("--photo_thres", type=float, default=0.3)
@@ -147,13 +152,32 @@ def load_model(args, dev) -> Pipeline:
     return model.to(dev).eval()
 
 
+def check_feature_cache(args) -> int:
+    """--feature_cache N: 0 = off; N > 0 needs --dataset folder and N >= n_views"""
+    n = int(getattr(args, "feature_cache", 0) or 0)
+    if n < 0:
+        raise SystemExit(f"--feature_cache must be >= 0, got {n}")
+    if n > 0 and args.dataset != "folder":
+        raise SystemExit(f"--feature_cache {n} needs --dataset folder (scan folders with pair.txt), got --dataset {args.dataset}")
+    if n > 0 and n < args.n_views:
+        raise SystemExit(f"--feature_cache {n} is below --n_views {args.n_views}: a depth map's views must fit in the cache")
+    return n
+
+
 def save_depth(args) -> int:
+    cache_n = check_feature_cache(args)
     rank, local_rank, world = shard.init_distributed()
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
     dataset = make_dataset(args)
-    mine = shard.shard_indices(len(dataset), rank, world)
     model = load_model(args, dev)
+    if cache_n > 0:
+        # scan mode: a contiguous block of (scan, view) per rank, so the rank's depth maps share their images
+        from itermvs_amd.scan_cache import save_depth_cached
+        done = save_depth_cached(args, dataset, shard.shard_contiguous(len(dataset), rank, world), model, dev)
+        shard.barrier()
+        return done
+    mine = shard.shard_indices(len(dataset), rank, world)
     done = 0
     if args.dataset == "folder":
         return save_depth_folder(args, dataset, mine, model, dev)

@@ -33,7 +33,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define ITERMVS_ABI_VERSION 16
+#define ITERMVS_ABI_VERSION 17
 #define ITERMVS_MAX_SRC 16     /* source views per reference view (pair.txt holds 10) */
 #define ITERMVS_MAX_HYP 8      /* hypotheses per level in the iteration branch (4,4,2) */
 #define ITERMVS_GROUPS 8       /* models/itermvs.py:28  */
@@ -206,6 +206,28 @@ typedef struct itermvs_corr_init_params {
 } itermvs_corr_init_params;
 
 int itermvs_corr_init(const itermvs_corr_init_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Slot forms of itermvs_corr_iter / itermvs_corr_init (scan mode: each image's feature pyramid is computed once and kept
+ * in a per-level slab; the reference recomputes FeatureNet on all V views of every sample, models/net.py:52-65 called per
+ * sample from eval.py:128-133).  The source map of (batch item b, view s) is read at
+ *     slab + slot[b * S + s] * slot_stride        (elements of `dtype`)
+ * so one captured graph serves every reference view: a replay refreshes the device slot table, not kernel arguments.
+ * Entries outside [0, n_slots) are clamped into it (a wrong map, never memory outside the slab).  Same arithmetic and tap
+ * order as the direct forms, bit for bit; the parameter block is the same, its `src` member is ignored.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct itermvs_level_slots {
+    const void* slab;                    /* slot 0; elements of `dtype`, 16-byte aligned */
+    int64_t slot_stride;                 /* elements between two slots (>= H * sy)       */
+    int64_t sc, sy, sx;                  /* channel (must be 1), row, column strides     */
+    int32_t C, H, W;
+    int32_t dtype;                       /* itermvs_dtype (all levels of one call share it) */
+    int32_t n_slots;                     /* slots in the slab                            */
+    const int32_t* slot;                 /* DEVICE [B,S] slot table                      */
+} itermvs_level_slots;
+
+int itermvs_corr_iter_slots(const itermvs_corr_iter_params* p, const itermvs_level_slots src[3], void* stream);
+int itermvs_corr_init_slots(const itermvs_corr_init_params* p, const itermvs_level_slots* src, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * itermvs_tap_indices -- diagnostic: the bilinear tap indices the FUSED kernels use (models/module.py:99-115 followed by

@@ -14,7 +14,7 @@ MAX_SRC = 16
 MAX_HYP = 8
 GROUPS = 8
 F32, F16, BF16 = 0, 1, 2      # itermvs_dtype: storage type of feature maps
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libitermvs_hip.so")
@@ -32,6 +32,13 @@ class LevelSrc(C.Structure):
     """itermvs_level_src"""
     _fields_ = [("view", C.c_void_p * MAX_SRC), ("sb", C.c_int64), ("sc", C.c_int64), ("sy", C.c_int64),
                 ("sx", C.c_int64), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("dtype", C.c_int32)]
+
+
+class LevelSlots(C.Structure):
+    """itermvs_level_slots: one pyramid level of a slab of cached maps + the device [B,S] slot table"""
+    _fields_ = [("slab", C.c_void_p), ("slot_stride", C.c_int64), ("sc", C.c_int64), ("sy", C.c_int64), ("sx", C.c_int64),
+                ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("dtype", C.c_int32), ("n_slots", C.c_int32),
+                ("slot", C.c_void_p)]
 
 
 class CorrIterParams(C.Structure):
@@ -101,6 +108,8 @@ PROTOTYPES = {
     "itermvs_box_chase": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "itermvs_corr_iter": (C.c_int, [C.POINTER(CorrIterParams), C.c_void_p]),
     "itermvs_corr_init": (C.c_int, [C.POINTER(CorrInitParams), C.c_void_p]),
+    "itermvs_corr_iter_slots": (C.c_int, [C.POINTER(CorrIterParams), C.POINTER(LevelSlots), C.c_void_p]),
+    "itermvs_corr_init_slots": (C.c_int, [C.POINTER(CorrInitParams), C.POINTER(LevelSlots), C.c_void_p]),
     "itermvs_tap_indices": (C.c_int, [C.POINTER(TapParams), C.c_void_p]),
     "itermvs_corr_iter_backward": (C.c_int, [C.POINTER(CorrIterParams), C.POINTER(C.c_void_p * 3),
                                              C.POINTER(C.POINTER(C.c_void_p) * 3), C.c_void_p, C.c_void_p]),

@@ -30,8 +30,11 @@ constexpr int kIterTW = ITERMVS_CORR_TW;      // a power of two, >= 4, dividing 
 // ---------------------------------------------------------------------------------------------
 // iteration branch
 // ---------------------------------------------------------------------------------------------
-template <int CPG, int TILE, int FT>
-__device__ __forceinline__ void corr_iter_level(const IterArgs& a, const IterLevel& L, int lvl, float* __restrict__ lds) {
+// SLOTS (itermvs_corr_iter_slots): the S source maps of batch item b are slots slot[b * S + s] of one slab per level --
+// L.src[0] is the slab, L.sb the slot stride; the index is uniform per (b, s).  Otherwise the same code, tap for tap.
+template <int CPG, int TILE, int FT, bool SLOTS = false>
+__device__ __forceinline__ void corr_iter_level(const IterArgs& a, const IterLevel& L, int lvl, float* __restrict__ lds,
+                                                const int32_t* __restrict__ slot = nullptr, int n_slots = 0) {
     using K = Chunk<CPG>;
     constexpr int LS = TILE + 1;  // padded LDS row: the transposed writes hit distinct banks
     const int N = L.N;
@@ -108,8 +111,11 @@ __device__ __forceinline__ void corr_iter_level(const IterArgs& a, const IterLev
                     const Footprint tp = quad_footprint(mine, k);
                     const float wv = quad_bcast(w_mine, k);
                     float corr[NGL];
-                    if constexpr (FT == ITERMVS_F32) chunk_corr<CPG, FT>(feat_base<FT>(L.src[s0 + k], (int64_t)b * L.sb), joff, tp, refv, corr);
-                    else chunk_corr16<CPG, FT>(feat_base<FT>(L.src[s0 + k], (int64_t)b * L.sb), j, tp, refv, corr);
+                    const float* fs;
+                    if constexpr (SLOTS) fs = feat_base<FT>(L.src[0], (int64_t)slot_index(slot, b * a.S + s0 + k, n_slots) * L.sb);
+                    else fs = feat_base<FT>(L.src[s0 + k], (int64_t)b * L.sb);
+                    if constexpr (FT == ITERMVS_F32) chunk_corr<CPG, FT>(fs, joff, tp, refv, corr);
+                    else chunk_corr16<CPG, FT>(fs, j, tp, refv, corr);
 #pragma unroll
                     for (int q = 0; q < NGL; ++q) acc[q] = acc[q] + corr[q] * wv;  // itermvs.py:115
                     wsum = wsum + wv;                                                // itermvs.py:116
@@ -154,6 +160,25 @@ __global__ void __launch_bounds__(kThreads) corr_iter_kernel(const IterArgs a) {
     }
 }
 
+// the slot form (itermvs_corr_iter_slots): one slot table and slab count per level
+struct IterSlotArgs {
+    IterArgs a;
+    const int32_t* slot[3];
+    int n_slots[3];
+};
+
+template <int TILE, int FT>
+__global__ void __launch_bounds__(kThreads) corr_iter_slots_kernel(const IterSlotArgs sa) {
+    __shared__ float lds[ITERMVS_MAX_HYP * ITERMVS_GROUPS * (TILE + 1)];
+    const int lvl = blockIdx.y;
+    const IterLevel& L = sa.a.lv[lvl];
+    switch (L.C) {
+        case 16: corr_iter_level<2, TILE, FT, true>(sa.a, L, lvl, lds, sa.slot[lvl], sa.n_slots[lvl]); break;
+        case 32: corr_iter_level<4, TILE, FT, true>(sa.a, L, lvl, lds, sa.slot[lvl], sa.n_slots[lvl]); break;
+        default: corr_iter_level<6, TILE, FT, true>(sa.a, L, lvl, lds, sa.slot[lvl], sa.n_slots[lvl]); break;
+    }
+}
+
 #ifdef ITERMVS_ITER_TWO_PHASE       // A/B builds only: measured and not shipped (experiments/corr_iter_two_phase.inc)
 #include "experiments/corr_iter_two_phase.inc"
 #endif
@@ -186,8 +211,10 @@ constexpr int kInitNB = 8;  // hypotheses per block
 #endif
 constexpr int kInitPad = ITERMVS_INIT_PAD;
 
-template <int CPG, int TILE, int FT>
-__device__ __forceinline__ void corr_init_body(const InitArgs& a, float* __restrict__ lds) {
+// SLOTS (itermvs_corr_init_slots): a.src[0] is the slab, a.sb the slot stride, view s of item b is slot[b * S + s]
+template <int CPG, int TILE, int FT, bool SLOTS = false>
+__device__ __forceinline__ void corr_init_body(const InitArgs& a, float* __restrict__ lds, const int32_t* __restrict__ slot = nullptr,
+                                               int n_slots = 0) {
     using K = Chunk<CPG>;
     constexpr int LS = TILE + kInitPad;
     const int nblocks = (a.N + a.NB - 1) / a.NB;
@@ -210,7 +237,8 @@ __device__ __forceinline__ void corr_init_body(const InitArgs& a, float* __restr
     const WarpRcp rc = make_rcp(g);
     const float inv_min = a.inv_min[b], inv_max = a.inv_max[b];
     const float* m = a.proj + ((size_t)b * a.S + s) * 12;
-    const float* fsrc = feat_base<FT>(a.src[s], (int64_t)b * a.sb);
+    const float* fsrc = SLOTS ? feat_base<FT>(a.src[0], (int64_t)slot_index(slot, b * a.S + s, n_slots) * a.sb)
+                              : feat_base<FT>(a.src[s], (int64_t)b * a.sb);
     const uint32_t sy = (uint32_t)a.sy * feat_bytes<FT>(), sx = (uint32_t)a.sx * feat_bytes<FT>();   // byte strides (chunk_corr)
 
     const int px_shift = (per_px & (per_px - 1)) == 0 ? 31 - __clz(per_px) : -1;      // (no integer division on the common path)
@@ -326,6 +354,22 @@ __global__ void __launch_bounds__(kThreads) corr_init_kernel(const InitArgs a) {
         case 16: corr_init_body<2, TILE, FT>(a, lds); break;
         case 32: corr_init_body<4, TILE, FT>(a, lds); break;
         default: corr_init_body<6, TILE, FT>(a, lds); break;
+    }
+}
+
+struct InitSlotArgs {
+    InitArgs a;
+    const int32_t* slot;
+    int n_slots;
+};
+
+template <int TILE, int FT>
+__global__ void __launch_bounds__(kThreads) corr_init_slots_kernel(const InitSlotArgs sa) {
+    __shared__ float lds[kInitNB * ITERMVS_GROUPS * (TILE + kInitPad)];
+    switch (sa.a.C) {
+        case 16: corr_init_body<2, TILE, FT, true>(sa.a, lds, sa.slot, sa.n_slots); break;
+        case 32: corr_init_body<4, TILE, FT, true>(sa.a, lds, sa.slot, sa.n_slots); break;
+        default: corr_init_body<6, TILE, FT, true>(sa.a, lds, sa.slot, sa.n_slots); break;
     }
 }
 
@@ -703,6 +747,102 @@ extern "C" int itermvs_corr_init(const itermvs_corr_init_params* p, void* stream
         case ITERMVS_F16: hipLaunchKernelGGL((corr_init_kernel<TILE, ITERMVS_F16>), grid, dim3(kThreads), 0, (hipStream_t)stream, a); break;
         case ITERMVS_BF16: hipLaunchKernelGGL((corr_init_kernel<TILE, ITERMVS_BF16>), grid, dim3(kThreads), 0, (hipStream_t)stream, a); break;
         default: hipLaunchKernelGGL((corr_init_kernel<TILE, ITERMVS_F32>), grid, dim3(kThreads), 0, (hipStream_t)stream, a); break;
+    }
+    itermvs_profile_end(2, (hipStream_t)stream);
+    return itermvs_launch_status();
+}
+
+// The slot forms: the same parameter blocks with p->src replaced by slab + slot table (include/itermvs_hip.h).
+extern "C" int itermvs_corr_iter_slots(const itermvs_corr_iter_params* p, const itermvs_level_slots* src, void* stream) {
+    ITERMVS_RETURN_IF(!p || !src, ITERMVS_ERR_NULL);
+    ITERMVS_RETURN_IF(p->B < 1 || p->H < 1 || p->W < 1, ITERMVS_ERR_DIMS);
+    ITERMVS_RETURN_IF(p->S < 1 || p->S > ITERMVS_MAX_SRC, ITERMVS_ERR_VIEWS);
+    ITERMVS_RETURN_IF(!p->ref_q || !p->proj || !p->view_w || !p->inv_depth_min || !p->inv_depth_max, ITERMVS_ERR_NULL);
+    ITERMVS_RETURN_IF(((uintptr_t)p->ref_q) % 16, ITERMVS_ERR_ALIGN);
+    for (int l = 0; l < 3; ++l) {
+        const int rc = itermvs_check_slots(src[l]);
+        if (rc) return rc;
+        ITERMVS_RETURN_IF(p->N[l] < 1 || p->N[l] > ITERMVS_MAX_HYP, ITERMVS_ERR_DIMS);
+        ITERMVS_RETURN_IF(!p->out[l], ITERMVS_ERR_NULL);
+        ITERMVS_RETURN_IF(!p->depth[l] && !p->norm_depth, ITERMVS_ERR_NULL);
+    }
+    ITERMVS_RETURN_IF(p->impl != 0, ITERMVS_ERR_DIMS);
+    const int dtype = src[0].dtype;
+    ITERMVS_RETURN_IF(src[1].dtype != dtype || src[2].dtype != dtype, ITERMVS_ERR_DTYPE);
+    IterSlotArgs sa;
+    IterArgs& a = sa.a;
+    int coff = 0;
+    for (int l = 0; l < 3; ++l) {
+        IterLevel& L = a.lv[l];
+        for (int v = 0; v < ITERMVS_MAX_SRC; ++v) L.src[v] = (const float*)src[l].slab;
+        L.sb = src[l].slot_stride; L.sy = src[l].sy; L.sx = src[l].sx;
+        L.depth = p->depth[l];
+        L.out = p->out[l];
+        for (int n = 0; n < ITERMVS_MAX_HYP; ++n) L.offs[n] = p->offsets[l][n];
+        L.C = src[l].C; L.H1 = src[l].H; L.W1 = src[l].W; L.N = p->N[l];
+        L.coff = coff;
+        coff += L.C;
+        sa.slot[l] = src[l].slot;
+        sa.n_slots[l] = src[l].n_slots;
+    }
+    a.ref_q = p->ref_q; a.proj = p->proj; a.view_w = p->view_w; a.nd = p->norm_depth; a.nd_sb = p->norm_depth_sb;
+    a.inv_min = p->inv_depth_min; a.inv_max = p->inv_depth_max;
+    a.B = p->B; a.S = p->S; a.H = p->H; a.W = p->W; a.CQ = coff;
+    a.band = 0;
+    if (p->view_w_sb == 0 && p->view_w_ss == 0 && p->view_w_sp == 0) {
+        a.vw_sp = 1; a.vw_ss = (int64_t)p->H * p->W; a.vw_sb = a.vw_ss * p->S;
+    } else {
+        ITERMVS_RETURN_IF(p->view_w_ss < 1 || p->view_w_sp < 1 || p->view_w_sb < 0, ITERMVS_ERR_LAYOUT);
+        a.vw_sb = p->view_w_sb; a.vw_ss = p->view_w_ss; a.vw_sp = p->view_w_sp;
+    }
+    itermvs_profile_begin(1, (hipStream_t)stream);
+    {
+        constexpr int TILE = 32;
+        const int tiles_x = (p->W + kIterTW - 1) / kIterTW;
+        const int tiles = tiles_x * ((p->H + TILE / kIterTW - 1) / (TILE / kIterTW));
+        a.band = iter_band_tiles(tiles_x, tiles, p);
+        const dim3 grid(a.band > 0 ? xcd_chunked_grid(tiles, a.band) : (unsigned)(((tiles + 7) / 8) * 8), 3, p->B);
+        switch (dtype) {
+            case ITERMVS_F16: hipLaunchKernelGGL((corr_iter_slots_kernel<TILE, ITERMVS_F16>), grid, dim3(kThreads), 0, (hipStream_t)stream, sa); break;
+            case ITERMVS_BF16: hipLaunchKernelGGL((corr_iter_slots_kernel<TILE, ITERMVS_BF16>), grid, dim3(kThreads), 0, (hipStream_t)stream, sa); break;
+            default: hipLaunchKernelGGL((corr_iter_slots_kernel<TILE, ITERMVS_F32>), grid, dim3(kThreads), 0, (hipStream_t)stream, sa); break;
+        }
+    }
+    itermvs_profile_end(1, (hipStream_t)stream);
+    return itermvs_launch_status();
+}
+
+extern "C" int itermvs_corr_init_slots(const itermvs_corr_init_params* p, const itermvs_level_slots* src, void* stream) {
+    ITERMVS_RETURN_IF(!p || !src, ITERMVS_ERR_NULL);
+    ITERMVS_RETURN_IF(p->B < 1 || p->H < 1 || p->W < 1 || p->N < 2, ITERMVS_ERR_DIMS);
+    ITERMVS_RETURN_IF(p->S < 1 || p->S > ITERMVS_MAX_SRC, ITERMVS_ERR_VIEWS);
+    ITERMVS_RETURN_IF(!p->ref.data || !p->proj || !p->inv_depth_min || !p->inv_depth_max || !p->out, ITERMVS_ERR_NULL);
+    const int rc = itermvs_check_slots(*src);
+    if (rc) return rc;
+    ITERMVS_RETURN_IF(p->ref.C != src->C || p->ref.H != p->H || p->ref.W != p->W, ITERMVS_ERR_DIMS);
+    ITERMVS_RETURN_IF(p->ref.dtype != src->dtype, ITERMVS_ERR_DTYPE);
+    ITERMVS_RETURN_IF(p->out_layout != 0 && p->out_layout != 1, ITERMVS_ERR_LAYOUT);
+    ITERMVS_RETURN_IF(p->out_layout == 1 && ((uintptr_t)p->out) % 16, ITERMVS_ERR_ALIGN);
+    InitSlotArgs sa;
+    InitArgs& a = sa.a;
+    for (int v = 0; v < ITERMVS_MAX_SRC; ++v) a.src[v] = (const float*)src->slab;
+    a.sb = src->slot_stride; a.sy = src->sy; a.sx = src->sx;
+    a.ref = p->ref; a.proj = p->proj; a.depth = p->depth;
+    a.inv_min = p->inv_depth_min; a.inv_max = p->inv_depth_max; a.out = p->out;
+    a.B = p->B; a.S = p->S; a.H = p->H; a.W = p->W; a.N = p->N;
+    a.C = src->C; a.H1 = src->H; a.W1 = src->W; a.NB = kInitNB;
+    a.out_cl = p->out_layout;
+    sa.slot = src->slot;
+    sa.n_slots = src->n_slots;
+    constexpr int TILE = 32;
+    const int nblocks = (p->N + kInitNB - 1) / kInitNB;
+    const int tiles = ((p->W + kIterTW - 1) / kIterTW) * ((p->H + TILE / kIterTW - 1) / (TILE / kIterTW));
+    const dim3 grid(((tiles + 7) / 8) * 8, p->S * nblocks, p->B);
+    itermvs_profile_begin(2, (hipStream_t)stream);
+    switch (src->dtype) {
+        case ITERMVS_F16: hipLaunchKernelGGL((corr_init_slots_kernel<TILE, ITERMVS_F16>), grid, dim3(kThreads), 0, (hipStream_t)stream, sa); break;
+        case ITERMVS_BF16: hipLaunchKernelGGL((corr_init_slots_kernel<TILE, ITERMVS_BF16>), grid, dim3(kThreads), 0, (hipStream_t)stream, sa); break;
+        default: hipLaunchKernelGGL((corr_init_slots_kernel<TILE, ITERMVS_F32>), grid, dim3(kThreads), 0, (hipStream_t)stream, sa); break;
     }
     itermvs_profile_end(2, (hipStream_t)stream);
     return itermvs_launch_status();

@@ -417,6 +417,13 @@ static inline unsigned xcd_chunked_grid(int tiles, int chunk) {
     return (unsigned)(8 * ((bands + 7) / 8) * chunk);
 }
 
+// slot of source view (b, s) in a slab (itermvs_level_slots): the table entry, clamped into [0, n_slots) so a stale or corrupt
+// table reads the wrong map instead of memory outside the slab.  Uniform per (b, s): the compiler may use a scalar load.
+__device__ __forceinline__ int slot_index(const int32_t* __restrict__ slot, int i, int n_slots) {
+    const int v = slot[i];
+    return v < 0 ? 0 : (v >= n_slots ? n_slots - 1 : v);
+}
+
 struct IterLevel {
     const float* src[ITERMVS_MAX_SRC];
     int64_t sb, sy, sx;
@@ -457,6 +464,22 @@ static inline int itermvs_check_level(const itermvs_level_src& s, int S) {
         ITERMVS_RETURN_IF(!s.view[v], ITERMVS_ERR_NULL);
         ITERMVS_RETURN_IF(((uintptr_t)s.view[v]) % 16, ITERMVS_ERR_ALIGN);
     }
+    return ITERMVS_OK;
+}
+
+// argument checks of one level of the slot forms (itermvs_corr_iter_slots / itermvs_corr_init_slots)
+static inline int itermvs_check_slots(const itermvs_level_slots& s) {
+    ITERMVS_RETURN_IF(!s.slab || !s.slot, ITERMVS_ERR_NULL);
+    ITERMVS_RETURN_IF(s.C != 16 && s.C != 32 && s.C != 48, ITERMVS_ERR_CHANNELS);
+    ITERMVS_RETURN_IF(s.H < 1 || s.W < 1 || s.n_slots < 1, ITERMVS_ERR_DIMS);
+    ITERMVS_RETURN_IF(s.sc != 1, ITERMVS_ERR_LAYOUT);
+    ITERMVS_RETURN_IF(s.dtype < ITERMVS_F32 || s.dtype > ITERMVS_BF16, ITERMVS_ERR_DTYPE);
+    ITERMVS_RETURN_IF(((uintptr_t)s.slab) % 16, ITERMVS_ERR_ALIGN);
+    const int64_t q = s.dtype == ITERMVS_F32 ? 4 : 8;          // 16-byte pixel vectors, as in itermvs_check_level
+    ITERMVS_RETURN_IF((s.sx % q) || (s.sy % q) || (s.slot_stride % q), ITERMVS_ERR_ALIGN);
+    ITERMVS_RETURN_IF(s.sx < s.C || s.sy < (int64_t)s.W * s.sx, ITERMVS_ERR_LAYOUT);
+    ITERMVS_RETURN_IF(s.slot_stride < (int64_t)s.H * s.sy, ITERMVS_ERR_LAYOUT);      // slots do not overlap
+    ITERMVS_RETURN_IF((int64_t)s.H * s.sy * (s.dtype == ITERMVS_F32 ? 4 : 2) >= (int64_t)1 << 32, ITERMVS_ERR_DIMS);
     return ITERMVS_OK;
 }
 

@@ -200,17 +200,31 @@ class InferenceEngine:
         y = ops.conv2d(x, wt, bias, stride=2, act="relu", split=(c, "none", sc))
         return self._cbr(y, name + "conv2.", 1, "relu", add=sc)
 
-    def feature_net(self, x: Tensor, compose=None) -> Dict[int, Tensor]:
+    def feature_net(self, x: Tensor, compose=None, out: Tuple[Tensor, Tensor, Tensor, Tensor] = None) -> Dict[int, Tensor]:
         """net.py:36-65 with BN folded; x [M,3,H,W] -> channels-last pyramids {1,2,3} (the layout the correlation kernels
         gather from); level 2 also keeps a planar copy (``o2_planar``) for the up-sampling head.
-        ``compose`` (see ops.stem): the camera composition rides in the stem launch; its results land in ``self.composed``."""
+        ``compose`` (see ops.stem): the camera composition rides in the stem launch; its results land in ``self.composed``.
+        ``out`` = (level 1, level 2, level 3, planar level 2): destinations the four maps are written to instead of fresh
+        tensors -- e.g. M consecutive slots of a ``FeatureSlab`` (scan mode); levels dense channels-last in ``feature_dtype``,
+        the planar map dense fp32."""
         p = "feature_net."
         m, _, hh, ww = x.shape
         dev = x.device
-        cl = lambda c, s: torch.empty((m, c, hh // s, ww // s), device=dev, dtype=self.feature_dtype,
-                                      memory_format=torch.channels_last)
-        o1, o2, o3 = cl(16, 2), cl(32, 4), cl(48, 8)
-        self.o2_planar = torch.empty((m, 32, hh // 4, ww // 4), device=dev)
+        if out is not None:
+            o1, o2, o3, self.o2_planar = out
+            want = [((m, 16, hh // 2, ww // 2), self.feature_dtype), ((m, 32, hh // 4, ww // 4), self.feature_dtype),
+                    ((m, 48, hh // 8, ww // 8), self.feature_dtype)]
+            for t, (shape, dt) in zip((o1, o2, o3), want):
+                if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous(memory_format=torch.channels_last):
+                    raise RuntimeError(f"feature_net: out level must be a dense channels-last {dt} tensor {shape}")
+            p2 = self.o2_planar
+            if tuple(p2.shape) != (m, 32, hh // 4, ww // 4) or p2.dtype != torch.float32 or not p2.is_contiguous():
+                raise RuntimeError(f"feature_net: the planar level-2 map must be a contiguous float32 {(m, 32, hh // 4, ww // 4)}")
+        else:
+            cl = lambda c, s: torch.empty((m, c, hh // s, ww // s), device=dev, dtype=self.feature_dtype,
+                                          memory_format=torch.channels_last)
+            o1, o2, o3 = cl(16, 2), cl(32, 4), cl(48, 8)
+            self.o2_planar = torch.empty((m, 32, hh // 4, ww // 4), device=dev)
         # conv1 + layer1[0].conv1 / .downsample in one launch, fea0 never leaves LDS (+ the camera composition, module.py:77-90)
         # (bf16x3 arithmetic: the stem's two results go to the chain kernel as channel quads -- 16-byte stores and loads)
         if compose is not None:
@@ -340,7 +354,7 @@ class InferenceEngine:
                    trace: dict = None) -> Tensor:
         """itermvs.py:36-70 + :159-164: view weights [B,S,h,w] (returned) and the initial hidden state (``hidden``, ``hx``)"""
         b, _, h3, w3 = ref3.shape
-        s = len(src3)
+        s = src3.S if isinstance(src3, ops.SlotSource) else len(src3)
         w = self.w
         # [B,S,32,8,h3,w3]; bf16x3 arithmetic: stored groups last -- PixelViewWeight's 3x3 layer then stages a pixel's 8 group
         # correlations with two 16-byte loads instead of eight dwords (its staging was 21 of its 24 us)
@@ -441,7 +455,6 @@ class InferenceEngine:
         ref = {l: per_view[l][:, 0] for l in (1, 2, 3)}
         h, wd = feats[2].shape[2:]
         ws = self._workspace(b, h, wd)
-        hx = ws["hx"]
 
         f2p = self.o2_planar
         ref2_nchw = f2p[:1] if b == 1 else f2p.view(b, v, *f2p.shape[1:])[:, 0].contiguous()
@@ -472,13 +485,23 @@ class InferenceEngine:
         else:
             proj, inv_min, inv_max = self.composed
         proj = proj.view(3, b, s, 12)
+        if trace is not None:
+            trace["feats"] = feats
+        return self._match(ws, src, ref[3], ref_q, up_logits, proj, inv_min, inv_max, trace, ev_rq, side)
 
-        view_w = self.stage_init(ws, src[3], ref[3], proj[2], inv_min, inv_max, trace)          # itermvs.py:270-276
+    def _match(self, ws: dict, src, ref3: Tensor, ref_q: Tensor, up_logits: Tensor, proj: Tensor, inv_min: Tensor,
+               inv_max: Tensor, trace: dict = None, ev_rq=None, side=None) -> Tuple[Tensor, Tensor]:
+        """everything of ``run`` after FeatureNet, the reference features on the 1/4 grid and the up-sampling weights:
+        initialisation, the GRU iterations and the final up-sampling.  ``src`` = per level the S source maps, or an
+        ``ops.SlotSource`` (``run_cached``)."""
+        main = torch.cuda.current_stream(self.device)
+        hx = ws["hx"]
+        view_w = self.stage_init(ws, src[3], ref3, proj[2], inv_min, inv_max, trace)             # itermvs.py:270-276
         logits, best = self.stage_head(ws, trace is not None)
         if ev_rq is not None:
             main.wait_event(ev_rq)                                      # the first corr_iter launch reads ref_q
         if trace is not None:
-            trace.update(feats=feats, proj=proj, ref_q=ref_q, logits0=logits, nd0=hx[:, HIDDEN:HIDDEN + 1].clone(), best0=best,
+            trace.update(proj=proj, ref_q=ref_q, logits0=logits, nd0=hx[:, HIDDEN:HIDDEN + 1].clone(), best0=best,
                          up_logits=up_logits, iters=[])
 
         conf = None
@@ -503,6 +526,79 @@ class InferenceEngine:
             main.wait_stream(side)                                      # the up-sampling weights
         # convex up-sampling of the depth and bilinear up-sampling of the confidence: one launch     itermvs.py:321-324
         return ops.final_upsample(up_logits, hx, inv_min, inv_max, conf, nd_channel=HIDDEN)
+
+    # -- scan mode: FeatureNet once per image, matching from a slab of cached pyramids --------------
+    def new_slab(self, n_slots: int, height: int, width: int) -> "FeatureSlab":
+        """a slab of ``n_slots`` image pyramids for images of ``height`` x ``width`` in this engine's ``feature_dtype``"""
+        return FeatureSlab(n_slots, height, width, self.feature_dtype, self.device)
+
+    def features_into(self, slab: "FeatureSlab", x: Tensor, slots) -> None:
+        """FeatureNet of the images x [K,3,H,W] straight into ``slots`` (K slot indices) of ``slab``: one FeatureNet call per
+        run of consecutive slots (a batch item's pyramid does not depend on the other items of its batch)."""
+        slots = [int(i) for i in slots]
+        if x.shape[0] != len(slots):
+            raise RuntimeError(f"features_into: {x.shape[0]} images for {len(slots)} slots")
+        if slab.dtype != self.feature_dtype or tuple(x.shape[2:]) != (slab.height, slab.width):
+            raise RuntimeError("features_into: the slab was made for another image size or feature_dtype")
+        i = 0
+        while i < len(slots):
+            j = i + 1
+            while j < len(slots) and slots[j] == slots[j - 1] + 1:
+                j += 1
+            a, k = slots[i], j - i
+            if a < 0 or a + k > slab.n_slots:
+                raise RuntimeError(f"features_into: slots {slots[i:j]} outside the slab's {slab.n_slots}")
+            self.feature_net(x[i:j].contiguous(), out=slab.slice(a, k))
+            i = j
+
+    def run_cached(self, slab: "FeatureSlab", ref_slot, src_slots, projs, depth_min: Tensor, depth_max: Tensor,
+                   composed: Tensor = None, trace: dict = None) -> Tuple[Tensor, Tensor]:
+        """``run`` from cached pyramids: everything after FeatureNet, with the reference view's maps taken from slot
+        ``ref_slot[b]`` of ``slab`` and source view s of item b read IN PLACE from slot ``src_slots[b][s]`` by the slot forms of
+        corr_init / corr_iter (itermvs_corr_*_slots).  ``src_slots``: [B,S] nested list or int32 device tensor; ``projs`` /
+        ``depth_min`` / ``depth_max`` / ``composed`` as in ``run`` (V = S + 1 cameras, view 0 the reference).  Bit for bit
+        the result of ``run`` on the same images; the camera composition runs in the launch that packs the reference
+        features (ref_quarter_compose) instead of the stem."""
+        refs = [int(r) for r in ref_slot]
+        b = len(refs)
+        if any(not 0 <= r < slab.n_slots for r in refs):
+            raise RuntimeError(f"run_cached: reference slots {refs} outside the slab's {slab.n_slots}")
+        if b == 1:
+            ref = {l: slab.levels[l][refs[0]:refs[0] + 1] for l in (1, 2, 3)}
+            ref2 = slab.planar[refs[0]:refs[0] + 1]
+        else:
+            idx = torch.tensor(refs, device=self.device)
+            ref = {l: slab.levels[l].index_select(0, idx).contiguous(memory_format=torch.channels_last) for l in (1, 2, 3)}
+            ref2 = slab.planar.index_select(0, idx)
+        slot = slab.slot_table(src_slots, b)
+        return self._run_cached(slab, ref, ref2, slot, projs, depth_min, depth_max, composed, trace)
+
+    def _run_cached(self, slab: "FeatureSlab", ref: Dict[int, Tensor], ref2: Tensor, slot: Tensor, projs, depth_min: Tensor,
+                    depth_max: Tensor, composed: Tensor = None, trace: dict = None) -> Tuple[Tensor, Tensor]:
+        """``run_cached`` with the reference maps given ({1,2,3}: [B,C,h,w] channels-last, ``ref2``: planar level 2) and the
+        slot table on the device (int32 [B,S]) -- the form ``CachedRunner`` captures"""
+        if self.side_branch:
+            raise RuntimeError("run_cached: side_branch=True is not supported in scan mode (it was measured slower; use the default)")
+        b, s = slot.shape
+        v = s + 1
+        h, wd = ref[2].shape[2:]
+        ws = self._workspace(b, h, wd)
+        up_logits = self.upsample_logits(ref2, ws)                     # only needed by the final convex up-sampling
+        if composed is not None:
+            ref_q = ops.ref_quarter(ref[1], ref[2], ref[3])
+            proj = composed
+            inv_min, inv_max = 1.0 / depth_min, 1.0 / depth_max                    # itermvs.py:267-268 (IEEE division, as on the host)
+        else:
+            pstack = projs if torch.is_tensor(projs) else torch.stack([projs[1], projs[2], projs[3]])
+            if self.projection == "host_fp32":
+                ref_q = ops.ref_quarter(ref[1], ref[2], ref[3])
+                proj, inv_min, inv_max = self.compose_on_host(pstack.reshape(3, b, v, 4, 4), depth_min, depth_max)
+            else:       # the same fp64 composition as the stem's (compose.hpp), in the launch that packs the reference features
+                ref_q, proj, inv_min, inv_max = ops.ref_quarter_compose(ref[1], ref[2], ref[3], pstack.reshape(3 * b, v, 4, 4),
+                                                                        self.nan_flag, (depth_min, depth_max))
+        proj = proj.view(3, b, s, 12)
+        src = {l: ops.SlotSource(slab.levels[l], slot, f"slab level {l}") for l in (1, 2, 3)}
+        return self._match(ws, src, ref[3], ref_q, up_logits, proj, inv_min, inv_max, trace)
 
     def compose_on_host(self, pstack: Tensor, depth_min: Tensor, depth_max: Tensor):
         """module.py:77-90 on the host in fp32, operation for operation (``projection="host_fp32"``): pstack [3,B,V,4,4] ->
@@ -655,6 +751,170 @@ class GraphedRunner:
     def replay(self):
         """launch the captured graph on the current stream as it is (static inputs already hold the sample)"""
         cur = torch.cuda.current_stream(self.imgs.device)
+        self._replay_streams.setdefault(cur.cuda_stream, cur)
+        self.graph.replay()
+        return self.out
+
+
+class FeatureSlab:
+    """Device memory of scan mode: ``n_slots`` image pyramids as FeatureNet leaves them -- ``levels`` {1,2,3}: [N,C,H/2^l,W/2^l]
+    channels-last in the engine's ``feature_dtype`` (what the correlation kernels gather from), ``planar``: the fp32 planar level-2
+    map [N,32,H/4,W/4] (the up-sampling head's input).  Slot i of every tensor belongs to one image."""
+
+    def __init__(self, n_slots: int, height: int, width: int, dtype: torch.dtype, device):
+        if n_slots < 1:
+            raise ValueError("FeatureSlab: need at least one slot")
+        if height % 32 or width % 32:
+            raise RuntimeError(f"image height and width must be multiples of 32, got {height}x{width}")
+        self.n_slots, self.height, self.width, self.dtype, self.device = n_slots, height, width, dtype, torch.device(device)
+        cl = lambda c, s: torch.empty((n_slots, c, height // s, width // s), device=device, dtype=dtype,
+                                      memory_format=torch.channels_last)
+        self.levels = {1: cl(16, 2), 2: cl(32, 4), 3: cl(48, 8)}
+        self.planar = torch.empty((n_slots, 32, height // 4, width // 4), device=device)
+
+    @staticmethod
+    def bytes_per_image(height: int, width: int, dtype: torch.dtype) -> int:
+        e = torch.empty((), dtype=dtype).element_size()
+        px = lambda s: (height // s) * (width // s)
+        return e * (16 * px(2) + 32 * px(4) + 48 * px(8)) + 4 * 32 * px(4)
+
+    @property
+    def nbytes(self) -> int:
+        return self.n_slots * self.bytes_per_image(self.height, self.width, self.dtype)
+
+    def slice(self, first: int, count: int):
+        """(level 1, level 2, level 3, planar level 2) of slots first .. first+count-1 -- ``InferenceEngine.feature_net``'s ``out``"""
+        return tuple(t[first:first + count] for t in (self.levels[1], self.levels[2], self.levels[3], self.planar))
+
+    def slot_table(self, src_slots, b: int) -> Tensor:
+        """[B,S] slot indices (nested list, or an int32 device tensor) -> contiguous int32 device tensor; every index is checked
+        against the slab (on the host: a device tensor is taken as it is -- the kernels clamp its entries into the slab)"""
+        if torch.is_tensor(src_slots):
+            if src_slots.dtype != torch.int32 or src_slots.device != self.device or src_slots.dim() != 2 or src_slots.shape[0] != b:
+                raise RuntimeError(f"slot table: expected an int32 tensor [B={b},S] on {self.device}")
+            return src_slots.contiguous()
+        rows = [[int(i) for i in r] for r in src_slots]
+        if len(rows) != b or not rows or len({len(r) for r in rows}) != 1:
+            raise RuntimeError(f"slot table: expected {b} rows of equal length")
+        if any(not 0 <= i < self.n_slots for r in rows for i in r):
+            raise RuntimeError(f"slot table: slot indices must lie in [0, {self.n_slots})")
+        return torch.tensor(rows, dtype=torch.int32).to(self.device, non_blocking=False)
+
+
+class _PinnedRing:
+    """host tensors -> a static device buffer in stream order without synchronising the stream: a ring of pinned buffers,
+    each reused only after the copy that last read it has completed (see GraphedRunner._stage_composed)"""
+
+    def __init__(self, dev_buf: Tensor, depth: int = 4):
+        self.dev = dev_buf
+        self.pin = [torch.empty(tuple(dev_buf.shape), dtype=dev_buf.dtype).pin_memory() for _ in range(depth)]
+        self.ev = [None] * depth
+        self.i = 0
+
+    def put(self, host: Tensor) -> None:
+        i = self.i
+        self.i = (i + 1) % len(self.pin)
+        if self.ev[i] is not None:
+            self.ev[i].synchronize()
+        self.pin[i].copy_(host)
+        self.dev.copy_(self.pin[i], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.ev[i] = ev
+
+
+class CachedRunner:
+    """Scan mode's captured form: ``InferenceEngine.run_cached`` as ONE hipGraph per (image shape, S, B) that serves every
+    reference view of every scan held in ``slab``.  The graph reads the source views through a static device slot table;
+    a call refreshes only the small static inputs -- the slot table (pinned ring), the reference view's maps (staged from
+    their slots, one itermvs_copy_multi launch together with the cameras and the depth range) -- and replays.  Outputs are
+    static buffers, overwritten by the next replay.  The NaN flag keeps its deferred semantics (``check_projection_finite``)."""
+
+    def __init__(self, engine: InferenceEngine, slab: FeatureSlab, batch: int, n_src: int, host_composed: bool = False,
+                 stream: "torch.cuda.Stream" = None):
+        if engine.side_branch:
+            raise RuntimeError("CachedRunner: side_branch=True is not supported in scan mode")
+        if engine.projection == "host_fp32" and not host_composed:
+            raise RuntimeError("CachedRunner: projection='host_fp32' is captured with host_composed=True (cameras on the host)")
+        dev = slab.device
+        self.engine, self.slab, self.b, self.s = engine, slab, batch, n_src
+        self.stream = stream or torch.cuda.Stream(device=dev)
+        v = n_src + 1
+        hh, ww = slab.height, slab.width
+        cl = lambda c, s: torch.empty((batch, c, hh // s, ww // s), device=dev, dtype=slab.dtype,
+                                      memory_format=torch.channels_last).zero_()
+        self.ref = {1: cl(16, 2), 2: cl(32, 4), 3: cl(48, 8)}
+        self.ref2 = torch.zeros((batch, 32, hh // 4, ww // 4), device=dev)
+        self.slot = torch.zeros((batch, n_src), device=dev, dtype=torch.int32)
+        self._slot_ring = _PinnedRing(self.slot)
+        self.depth_min = torch.ones((batch,), device=dev)
+        self.depth_max = torch.full((batch,), 2.0, device=dev)
+        self.composed = None
+        self.proj_stack = None
+        if host_composed:
+            self.composed = torch.zeros((3, batch, n_src, 12), device=dev)
+            self._comp_ring = _PinnedRing(self.composed)
+        else:
+            eye = torch.eye(4, device=dev).expand(3, batch, v, 4, 4)
+            self.proj_stack = eye.contiguous()
+        # (the warm-up runs read zero maps and identity cameras: finite, never flagged)
+        self._ws_token = next(engine._owner_tokens)
+        engine._ws_owner = self._ws_token
+        self._replay_streams = {self.stream.cuda_stream: self.stream}
+        weakref.finalize(self, _release_workspace, weakref.ref(engine), self._ws_token, self._replay_streams)
+        self.stream.wait_stream(torch.cuda.current_stream(dev))
+        run = lambda: engine._run_cached(slab, self.ref, self.ref2, self.slot, self.proj_stack, self.depth_min, self.depth_max,
+                                         composed=self.composed)
+        try:
+            with torch.cuda.stream(self.stream):
+                for _ in range(2):
+                    run()
+                torch.cuda.synchronize(dev)
+                self.graph = torch.cuda.CUDAGraph()
+                gc.collect()
+                gc_was_on = gc.isenabled()
+                gc.disable()
+                try:
+                    self.graph.capture_begin(capture_error_mode="thread_local")
+                    self.out = run()
+                    self.graph.capture_end()
+                finally:
+                    if gc_was_on:
+                        gc.enable()
+        finally:
+            engine._ws_owner = None
+        torch.cuda.synchronize(dev)
+
+    def __call__(self, ref_slot, src_slots, projs, depth_min: Tensor, depth_max: Tensor):
+        """one depth map per batch item: ``ref_slot`` [B] and ``src_slots`` [B,S] (host ints), ``projs`` {1,2,3: [B,V,4,4]} device
+        cameras (or, when captured with ``host_composed``, the CPU composed [3,B,S,12]), ``depth_min`` / ``depth_max`` [B] device.
+        Replays on the current stream; returns the static (depth, confidence) buffers."""
+        refs = [int(r) for r in ref_slot]
+        rows = [[int(i) for i in r] for r in src_slots]
+        n = self.slab.n_slots
+        if len(refs) != self.b or len(rows) != self.b or any(len(r) != self.s for r in rows):
+            raise RuntimeError(f"CachedRunner: captured for B={self.b}, S={self.s}")
+        if any(not 0 <= i < n for i in refs + [i for r in rows for i in r]):
+            raise RuntimeError(f"CachedRunner: slot indices must lie in [0, {n})")
+        self._slot_ring.put(torch.tensor(rows, dtype=torch.int32))
+        flat = lambda t: t.permute(0, 2, 3, 1).reshape(-1) if t.stride(1) == 1 and t.shape[1] > 1 else t.reshape(-1)
+        pairs = []
+        for bi, r in enumerate(refs):
+            for l in (1, 2, 3):
+                pairs.append((flat(self.ref[l][bi:bi + 1]), flat(self.slab.levels[l][r:r + 1])))
+            pairs.append((self.ref2[bi:bi + 1].reshape(-1), self.slab.planar[r:r + 1].reshape(-1)))
+        pairs += [(self.depth_min, depth_min.reshape(-1).float()), (self.depth_max, depth_max.reshape(-1).float())]
+        if self.composed is not None:
+            self._comp_ring.put(projs)
+        else:
+            pstack = projs if torch.is_tensor(projs) else torch.stack([projs[1], projs[2], projs[3]])
+            pairs.append((self.proj_stack, pstack.reshape(self.proj_stack.shape).float().contiguous()))
+        for i in range(0, len(pairs), 8):
+            ops.copy_multi([d for d, _ in pairs[i:i + 8]], [t for _, t in pairs[i:i + 8]])
+        return self.replay()
+
+    def replay(self):
+        cur = torch.cuda.current_stream(self.slab.device)
         self._replay_streams.setdefault(cur.cuda_stream, cur)
         self.graph.replay()
         return self.out

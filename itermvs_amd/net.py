@@ -155,6 +155,18 @@ class Pipeline(nn.Module):
         instead of calling check_projection_finite() (which synchronises)"""
         return None if self._engine is None else self._engine.nan_flag
 
+    def inference_engine(self):
+        """the test-mode ``InferenceEngine`` of the current weights and settings, packed on first use and re-packed after any
+        change ``invalidate`` covers (scan mode, ``itermvs_amd.scan_cache``, keys its cached pyramids on the returned object)"""
+        from .engine import InferenceEngine
+        if self._engine is not None and self._engine_version != self._weights_version():
+            self.invalidate()                 # parameters were updated in place since the weights were packed
+        if self._engine is None:
+            self._engine = InferenceEngine(self.weights(), self.iteration, self.feature_dtype, self.projection, self.conv_arithmetic,
+                                           self.side_branch)
+            self._engine_version = self._weights_version()
+        return self._engine
+
     def _apply(self, fn, *a, **k):
         self.invalidate()
         return super()._apply(fn, *a, **k)
@@ -181,13 +193,7 @@ class Pipeline(nn.Module):
         depth_min = depth_min.float().to(x.device)
         depth_max = depth_max.float().to(x.device)
         if self.test:
-            from .engine import InferenceEngine
-            if self._engine is not None and self._engine_version != self._weights_version():
-                self.invalidate()                 # parameters were updated in place since the weights were packed
-            if self._engine is None:
-                self._engine = InferenceEngine(self.weights(), self.iteration, self.feature_dtype, self.projection, self.conv_arithmetic,
-                                               self.side_branch)
-                self._engine_version = self._weights_version()
+            self.inference_engine()
             with torch.no_grad():
                 composed = None
                 if host_composed:

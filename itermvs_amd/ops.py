@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import MAX_HYP, MAX_SRC, ConvParams, CorrInitParams, CorrIterParams, FMap, LevelSrc, TapParams, check
+from ._lib import MAX_HYP, MAX_SRC, ConvParams, CorrInitParams, CorrIterParams, FMap, LevelSlots, LevelSrc, TapParams, check
 
 Tensor = torch.Tensor
 
@@ -70,6 +70,43 @@ def level_src(views: Sequence[Tensor], name: str = "src") -> LevelSrc:
     ls.sb, ls.sc, ls.sy, ls.sx = v0.stride()
     ls.C, ls.H, ls.W = v0.shape[1], v0.shape[2], v0.shape[3]
     return ls
+
+
+class SlotSource:
+    """The source views of one pyramid level read through a slot table (scan mode, ``itermvs_level_slots``): ``slab``
+    [n_slots,C,H1,W1] channels-last (fp32 / fp16 / bf16 storage) holds cached maps, ``slot`` (int32 device [B,S]) says which
+    slot is source view s of batch item b.  ``corr_iter`` / ``corr_init`` take it in place of the list of S views and launch
+    the slot form of the kernel (same arithmetic, bit for bit)."""
+
+    def __init__(self, slab: Tensor, slot: Tensor, name: str = "slab"):
+        _feat(slab, name)
+        if slab.dim() != 4 or slab.stride(1) != 1:
+            raise RuntimeError(f"{name}: expected a channels-last [n_slots,C,H,W] slab")
+        if not (isinstance(slot, torch.Tensor) and slot.is_cuda and slot.dtype == torch.int32 and slot.dim() == 2
+                and slot.is_contiguous()):
+            raise RuntimeError(f"{name}: the slot table must be a contiguous int32 device tensor [B,S]")
+        if slot.device != slab.device:
+            raise RuntimeError(f"{name}: slab and slot table must be on the same device")
+        if not 1 <= slot.shape[1] <= MAX_SRC:
+            raise RuntimeError(f"{name}: need 1..{MAX_SRC} source views, got {slot.shape[1]}")
+        self.slab, self.slot, self.name = slab, slot, name
+
+    @property
+    def S(self) -> int:
+        return self.slot.shape[1]
+
+    @property
+    def B(self) -> int:
+        return self.slot.shape[0]
+
+    def struct(self) -> LevelSlots:
+        t = self.slab
+        ls = LevelSlots()
+        ls.slab, ls.slot = t.data_ptr(), self.slot.data_ptr()
+        ls.slot_stride, ls.sc, ls.sy, ls.sx = t.stride()
+        ls.C, ls.H, ls.W = t.shape[1], t.shape[2], t.shape[3]
+        ls.dtype, ls.n_slots = _feat(t, self.name), t.shape[0]
+        return ls
 
 
 def channels_last(t: Tensor) -> Tensor:
@@ -217,13 +254,21 @@ def corr_iter(src: Dict[int, Sequence[Tensor]], ref_q: Tensor, proj: Tensor, vie
     ``depth[l]`` [B,N_l,H,W] or generated from ``norm_depth`` [B,1,H,W] + ``offsets[l]``.
     Returns the three aggregated group correlations [B,N_l,8,H,W]."""
     b, h, w, _ = ref_q.shape
-    s = len(src[1])
+    slots = None
+    if isinstance(src[1], SlotSource):          # scan mode: itermvs_corr_iter_slots
+        if not all(isinstance(src[l], SlotSource) and src[l].B == b and src[l].S == src[1].S for l in (1, 2, 3)):
+            raise RuntimeError("corr_iter: slot sources of all three levels must share the [B,S] table shape")
+        s = src[1].S
+        slots = (LevelSlots * 3)(*[src[l].struct() for l in (1, 2, 3)])
+    else:
+        s = len(src[1])
     p = CorrIterParams()
     p.B, p.S, p.H, p.W = b, s, h, w
     keep = []
     outs: List[Tensor] = []
     for i, l in enumerate((1, 2, 3)):
-        p.src[i] = level_src(src[l], f"src level {l}")
+        if slots is None:
+            p.src[i] = level_src(src[l], f"src level {l}")
         if depth is not None and depth.get(l) is not None:
             d = _dev(depth[l], "depth").contiguous()
             keep.append(d)
@@ -263,7 +308,10 @@ def corr_iter(src: Dict[int, Sequence[Tensor]], ref_q: Tensor, proj: Tensor, vie
     lib = _lib.load()
     if not timed:               # no timing events around this launch (itermvs_profile_*): mask bit 0 off for the call
         lib.itermvs_profile_set_mask(_PROFILE_MASK[0] & ~1)
-    check(lib.itermvs_corr_iter(C.byref(p), _stream()), "itermvs_corr_iter")
+    if slots is None:
+        check(lib.itermvs_corr_iter(C.byref(p), _stream()), "itermvs_corr_iter")
+    else:
+        check(lib.itermvs_corr_iter_slots(C.byref(p), slots, _stream()), "itermvs_corr_iter_slots")
     if not timed:
         lib.itermvs_profile_set_mask(_PROFILE_MASK[0])
     return outs
@@ -546,10 +594,17 @@ def corr_init(src3: Sequence[Tensor], ref3: Tensor, proj: Tensor, inv_min: Tenso
     as the [B,S,N,8,H,W] view of that storage -- as [B*S*N,8,H,W] it is a channels-last tensor, which conv2d's 8-channel bf16x3
     layer stages with two 16-byte loads per pixel, and view_aggregate(_up) reads it as it is."""
     b, _, h, w = ref3.shape
-    s = len(src3)
+    slots = None
+    if isinstance(src3, SlotSource):            # scan mode: itermvs_corr_init_slots
+        if src3.B != b:
+            raise RuntimeError("corr_init: the slot table must have one row per batch item")
+        s, slots = src3.S, src3.struct()
+    else:
+        s = len(src3)
     p = CorrInitParams()
     p.B, p.S, p.H, p.W, p.N = b, s, h, w, num_samples
-    p.src = level_src(src3, "src level 3")
+    if slots is None:
+        p.src = level_src(src3, "src level 3")
     p.ref = fmap(ref3, "ref3")
     proj = _dev(proj, "proj").contiguous()
     p.proj = proj.data_ptr()
@@ -575,7 +630,10 @@ def corr_init(src3: Sequence[Tensor], ref3: Tensor, proj: Tensor, inv_min: Tenso
     lib = _lib.load()
     if not timed:               # no timing events around this launch: mask bit 1 off for the call
         lib.itermvs_profile_set_mask(_PROFILE_MASK[0] & ~2)
-    check(lib.itermvs_corr_init(C.byref(p), _stream()), "itermvs_corr_init")
+    if slots is None:
+        check(lib.itermvs_corr_init(C.byref(p), _stream()), "itermvs_corr_init")
+    else:
+        check(lib.itermvs_corr_init_slots(C.byref(p), C.byref(slots), _stream()), "itermvs_corr_init_slots")
     if not timed:
         lib.itermvs_profile_set_mask(_PROFILE_MASK[0])
     return out

@@ -23,6 +23,17 @@ def shard_indices(n_items: int, rank: int, world: int) -> List[int]:
     return list(range(rank, n_items, world))
 
 
+def shard_contiguous(n_items: int, rank: int, world: int) -> List[int]:
+    """Block partition: rank r owns ONE contiguous block of the item list (sizes differ by at most one, the first
+    ``n_items % world`` ranks take the larger blocks).  Scan mode (eval.py --feature_cache) uses it on the global
+    (scan, reference view) list so that a rank's depth maps share their images and its feature cache hits."""
+    if not (0 <= rank < world):
+        raise ValueError(f"rank {rank} outside world of size {world}")
+    base, extra = divmod(n_items, world)
+    start = rank * base + min(rank, extra)
+    return list(range(start, start + base + (1 if rank < extra else 0)))
+
+
 def shard_counts(n_items: int, world: int) -> List[int]:
     return [len(range(r, n_items, world)) for r in range(world)]
 
