@@ -73,6 +73,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--photo_thres", type=float, default=0.3)
     p.add_argument("--num_samples", type=int, default=8, help="synthetic dataset: number of reference views")
     p.add_argument("--filter", action="store_true", help="fuse the saved depth maps of every scan into a point cloud (eval.py:311-325)")
+    p.add_argument("--fuse_points", default="host", choices=["host", "device"],
+                   help="--filter: where the surviving pixels become PLY vertices (eval.py:287-308): numpy on the host with one "
+                        "synchronisation per reference view (default), or itermvs_fuse_points on the GPU with one per group of views")
+    p.add_argument("--save_masks", action="store_true",
+                   help="--filter: write <outdir>/<scan>/mask/<view>_photo.png, _geo.png, _final.png like the reference (eval.py:266-269)")
     return p
 
 
@@ -266,7 +271,8 @@ def fuse_scans(args) -> int:
         scan = scans[i]
         stats = fusion.filter_depth(os.path.join(args.testpath, scan), os.path.join(args.outdir, scan),
                                     os.path.join(args.outdir, scan + ".ply"), args.geo_pixel_thres, args.geo_depth_thres,
-                                    args.photo_thres, device=dev, img_wh=tuple(args.img_wh))
+                                    args.photo_thres, device=dev, img_wh=tuple(args.img_wh), points=args.fuse_points,
+                                    save_masks=args.save_masks)
         for v, (g, ph, f) in stats.items():
             print("processing {}, ref-view{:0>2}, geo_mask:{:3f} photo_mask:{:3f} final_mask: {:3f}".format(scan, v, g, ph, f))
         n += 1

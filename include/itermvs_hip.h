@@ -33,7 +33,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define ITERMVS_ABI_VERSION 17
+#define ITERMVS_ABI_VERSION 18
 #define ITERMVS_MAX_SRC 16     /* source views per reference view (pair.txt holds 10) */
 #define ITERMVS_MAX_HYP 8      /* hypotheses per level in the iteration branch (4,4,2) */
 #define ITERMVS_GROUPS 8       /* models/itermvs.py:28  */
@@ -617,6 +617,35 @@ int itermvs_fuse_depth(const float* depth_ref, const float* conf_ref, const floa
                        float geo_depth_thres, float photo_thres, int32_t geo_mask_thres, double* depth_avg,
                        uint8_t* photo_mask, uint8_t* geo_mask, uint8_t* final_mask, int32_t* geo_sum,
                        void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * itermvs_fuse_points -- the tail of filter_depth for ONE reference view (eval.py:287-308): the pixels of `final_mask` are
+ *   unprojected (eval.py:287-294), coloured (eval.py:295-296) and appended to `records` as the PLY vertex element of
+ *   eval.py:298-308 (x, y, z little-endian float32; red, green, blue uint8: 15 bytes per vertex, unpadded), in row-major pixel
+ *   order (y, then x) behind the vertices of the views emitted before -- the order of the reference's boolean indexing.
+ *   Three launches on `stream` (count, single-workgroup scan, emit); no workgroup waits on another and nothing is accumulated
+ *   with atomics, so the bytes do not depend on scheduling.  Calls for consecutive views may be enqueued back to back: the host
+ *   reads nothing between them.
+ * depth_avg [H,W] fp64, final_mask / photo_mask / geo_mask [H,W] uint8 as itermvs_fuse_depth wrote them (photo_mask, geo_mask
+ *   may be NULL: they are only counted); cam: device [21] fp32 = inv(K_ref) (9) | rows 0..2 of inv(E_ref) (12), inverted on the
+ *   host in float32; rgb [H,W,3] uint8, the reference image at the depth maps' size (copied: (u / 255.f * 255) cast back to
+ *   uint8 is u for every byte value).
+ * Arithmetic: pixel indices as fp64, x*d, y*d, d, then (m0*p0 + m1*p1) + m2*p2 and ((..) + m2*p2) + m3*1.0 in fp64 without
+ *   fused multiply-add, one round-to-nearest conversion to fp32; non-finite values pass through.
+ * records: `capacity` vertices of 15 bytes, shared by the views of a flush group (may be NULL when capacity is 0);
+ * cursor: device uint64, vertices emitted so far: read as this view's first vertex index and advanced by its count ON THE DEVICE;
+ * view_counts: device int64 [n_views][4]; row `view` receives {pixels in photo_mask, in geo_mask, in final_mask, first vertex
+ *   index} (-1 for a mask that was not given).
+ * A vertex whose index is >= capacity is not stored; cursor and view_counts hold the true totals all the same, so the caller
+ *   sees the overflow (cursor > capacity) at its next synchronisation.  Nothing outside records[0 : 15 * capacity] is written.
+ * workspace: itermvs_fuse_points_workspace_bytes(H, W) bytes of device scratch (per-workgroup counts), reusable by the next
+ *   call on the same stream.  ITERMVS_ERR_DIMS: H or W < 1, H * W > 0x7fffff00 (32-bit pixel indices), capacity or view < 0.
+ * ------------------------------------------------------------------------------------------ */
+int itermvs_fuse_points_workspace_bytes(int32_t H, int32_t W);
+int itermvs_fuse_points(const double* depth_avg, const uint8_t* final_mask, const uint8_t* photo_mask,
+                        const uint8_t* geo_mask, const float* cam, const uint8_t* rgb, int32_t H, int32_t W,
+                        uint8_t* records, int64_t capacity, uint64_t* cursor, int64_t* view_counts, int32_t view,
+                        uint32_t* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * itermvs_image_pyramid -- the input side of the path: datasets/dtu_yao_eval.py:61-74

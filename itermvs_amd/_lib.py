@@ -14,7 +14,7 @@ MAX_SRC = 16
 MAX_HYP = 8
 GROUPS = 8
 F32, F16, BF16 = 0, 1, 2      # itermvs_dtype: storage type of feature maps
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libitermvs_hip.so")
@@ -172,6 +172,9 @@ PROTOTYPES = {
     "itermvs_fuse_depth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                      C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
+    "itermvs_fuse_points_workspace_bytes": (C.c_int, [C.c_int32, C.c_int32]),
+    "itermvs_fuse_points": (C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                      C.c_int32, C.c_void_p, C.c_void_p]),
     "itermvs_profile_graph_count": (C.c_int, []),
     "itermvs_profile_graph_read": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "itermvs_profile_collect": (C.c_int, [C.POINTER(C.c_int32), c_float_p, C.c_int32]),
