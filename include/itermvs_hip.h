@@ -658,6 +658,48 @@ int itermvs_image_pyramid(const uint8_t* src, int32_t V, int32_t Hs, int32_t Ws,
                           float* level1, float* level2, float* level3, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Training input side (csrc/train_input.hip).
+ *
+ * itermvs_image_pyramid_jitter -- datasets/dtu_yao.py:64-77 and datasets/blendedmvs.py:85-101 (read_img in train mode):
+ * transforms.ColorJitter(brightness=0.5, contrast=0.5) on the PIL image, then itermvs_image_pyramid's arithmetic.  The
+ * jitter is Pillow's (PIL/ImageEnhance.py Brightness / Contrast -> Image.blend(degenerate, image, (float)f)):
+ *   blend(a, b, f) = (uint8)(a + f * (b - a)), float32, clipped to 0..255 when f > 1;
+ *   brightness: a = 0;  contrast: a = int(mean(L) + 0.5) with L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 over the image
+ *   as it stands when contrast is applied.
+ * jitter [V] (device): one draw per view; enabled = 0 leaves the view's bytes as they are (level 0 then equals
+ *   itermvs_image_pyramid's).  lsum [V] (device uint64 scratch): zeroed and filled here with the per-view sum of L.
+ * Outputs as itermvs_image_pyramid (level1..3 may be NULL; H and W multiples of 8 when requested).  Two kernels and a memset.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct itermvs_jitter {
+    float brightness;            /* brightness factor (torchvision's draw, a float32 value) */
+    float contrast;              /* contrast factor */
+    int32_t contrast_first;      /* 1: contrast is applied before brightness (randperm puts index 1 ahead of index 0) */
+    int32_t enabled;             /* 0: no jitter (val mode) */
+} itermvs_jitter;
+
+int itermvs_image_pyramid_jitter(const uint8_t* src, int32_t V, int32_t Hs, int32_t Ws, int32_t H, int32_t W,
+                                 const itermvs_jitter* jitter, uint64_t* lsum, float* level0, float* level1, float* level2,
+                                 float* level3, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * itermvs_gt_pyramid -- the reference view's ground truth at the four levels, one launch for a batch of B samples:
+ *   ITERMVS_GT_DTU        datasets/dtu_yao.py:80-119: depth = raw * p0; cv2.resize(x1/2, NEAREST), centre crop to (W, H),
+ *                         level l = cv2.resize(crop, (W >> l, H >> l), NEAREST); mask = (depth_visual > 10) under the same map
+ *   ITERMVS_GT_BLENDEDMVS datasets/blendedmvs.py:62-83: depth = (raw * p0) * p1, resized NEAREST to (W, H), then to each level;
+ *                         mask = (depth >= p2) & (depth <= p3) at the FILE size, resized NEAREST straight to each level size
+ * NEAREST = cv2's map min(floor(d * (1.0 / ((double)dst / src))), src - 1) per axis.
+ * depth_rows [B,Hs,Ws] float32: the PFM payload as stored (rows bottom-up; the flip of data_io.py:38 is in the map).
+ * mask_src [B,Hs,Ws] uint8: depth_visual (DTU; unused for BlendedMVS).  params [B,4] float32 (device): p0..p3 above.
+ * depth_l / mask_l [B,1,H>>l,W>>l] float32, each may be NULL (skipped).  ITERMVS_ERR_DIMS: H or W not a multiple of 8, B < 1,
+ * DTU crop outside the x1/2 image, unknown recipe.
+ * ------------------------------------------------------------------------------------------ */
+#define ITERMVS_GT_DTU 0
+#define ITERMVS_GT_BLENDEDMVS 1
+int itermvs_gt_pyramid(const float* depth_rows, const uint8_t* mask_src, const float* params, int32_t B, int32_t Hs, int32_t Ws,
+                       int32_t H, int32_t W, int32_t recipe, float* depth0, float* depth1, float* depth2, float* depth3,
+                       float* mask0, float* mask1, float* mask2, float* mask3, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Training-mode BatchNorm (+ ReLU) of FeatureNet's ConvBnReLU / ConvBn layers (models/module.py:33-50 under
  * train.py:194-243; torch.nn.BatchNorm2d in train() mode): x, y, dy, dx are dense NCHW fp32 [N,C,H*W].
  *   forward : batch mean / biased variance per channel -> y = [relu]((x - mean) / sqrt(var + eps) * gamma + beta);

@@ -14,6 +14,7 @@ MAX_SRC = 16
 MAX_HYP = 8
 GROUPS = 8
 F32, F16, BF16 = 0, 1, 2      # itermvs_dtype: storage type of feature maps
+GT_DTU, GT_BLENDEDMVS = 0, 1  # itermvs_gt_pyramid recipes
 ABI_VERSION = 18
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -160,6 +161,8 @@ PROTOTYPES = {
                                        C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "itermvs_image_pyramid": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 5),
+    "itermvs_image_pyramid_jitter": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 7),
+    "itermvs_gt_pyramid": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 6 + [C.c_void_p] * 9),
     "itermvs_bn_workspace_floats": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "itermvs_bn_train_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                            C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -11,43 +11,16 @@
 // Uploading the uint8 image (5.8 MB for a 1600 x 1200 DTU view) instead of the float32 pyramid (29.5 MB) also cuts the
 // host-to-device traffic of a depth map five-fold.
 #include "common.hpp"
+#include "image_level0.hpp"
 
 namespace itermvs {
-
-__device__ __forceinline__ void resize_axis(int d, double scale, int n_src, int& s0, int& s1, float& a0, float& a1) {
-    float f = (float)(((double)d + 0.5) * scale - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    if (s < 0) { f = 0.0f; s = 0; }
-    if (s >= n_src - 1) { f = 0.0f; s = n_src - 1; }
-    s0 = s;
-    s1 = s + 1 < n_src ? s + 1 : n_src - 1;
-    a0 = 1.0f - f;
-    a1 = f;
-}
-
-__device__ __forceinline__ float normalise_u8(uint8_t v) {   // 2 * x / 255. - 1, float32 op by op
-    return (2.0f * (float)v) / 255.0f - 1.0f;
-}
 
 // thread per output pixel (v, y, x); src [V,Hs,Ws,3] uint8 interleaved RGB; out [V,3,H,W] float32 planes
 __global__ void image_level0_kernel(const uint8_t* __restrict__ src, int V, int Hs, int Ws, int H, int W, float* __restrict__ out) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (int64_t)V * H * W) return;
     const int x = (int)(t % W), y = (int)((t / W) % H), v = (int)(t / ((int64_t)W * H));
-    int x0, x1, y0, y1;
-    float ax0, ax1, ay0, ay1;
-    resize_axis(x, (double)Ws / (double)W, Ws, x0, x1, ax0, ax1);
-    resize_axis(y, (double)Hs / (double)H, Hs, y0, y1, ay0, ay1);
-    const uint8_t* s = src + (int64_t)v * Hs * Ws * 3;
-    const uint8_t* r0 = s + (int64_t)y0 * Ws * 3;
-    const uint8_t* r1 = s + (int64_t)y1 * Ws * 3;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float top = normalise_u8(r0[x0 * 3 + c]) * ax0 + normalise_u8(r0[x1 * 3 + c]) * ax1;   // horizontal pass
-        const float bot = normalise_u8(r1[x0 * 3 + c]) * ax0 + normalise_u8(r1[x1 * 3 + c]) * ax1;
-        out[(((int64_t)v * 3 + c) * H + y) * W + x] = top * ay0 + bot * ay1;                            // vertical pass
-    }
+    level0_pixel(src, v, Hs, Ws, H, W, x, y, out, [](uint8_t b) { return normalise_u8(b); });
 }
 
 // level l = mean of the central 2 x 2 pixels of each 2^l x 2^l block of level 0 (cv2.resize INTER_LINEAR at an exact
@@ -62,6 +35,12 @@ __global__ void image_down_kernel(const float* __restrict__ l0, int M, int H, in
     const float top = p[0] * 0.5f + p[1] * 0.5f;
     const float bot = p[W] * 0.5f + p[W + 1] * 0.5f;
     out[t] = top * 0.5f + bot * 0.5f;
+}
+
+int image_pyramid_down(const float* level0, int M, int H, int W, int lvl, float* out, hipStream_t stream) {
+    const int64_t n = (int64_t)M * (H >> lvl) * (W >> lvl);
+    hipLaunchKernelGGL(image_down_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, level0, M, H, W, lvl, out);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
 }  // namespace itermvs

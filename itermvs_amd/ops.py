@@ -1615,6 +1615,56 @@ def image_pyramid(raw: Tensor, height: int, width: int, all_levels: bool = True,
     return out
 
 
+JITTER_BYTES = 16      # sizeof(itermvs_jitter): brightness f32, contrast f32, contrast_first i32, enabled i32
+
+
+def image_pyramid_jitter(raw: Tensor, height: int, width: int, jitter: Tensor, all_levels: bool = True) -> Dict[str, Tensor]:
+    """datasets/dtu_yao.py:64-77 / blendedmvs.py:85-101 in train mode on the GPU: Pillow's ColorJitter(brightness=0.5,
+    contrast=0.5) per view, then ``image_pyramid``.  raw [V,Hs,Ws,3] uint8 (device); jitter: uint8 device tensor of V
+    itermvs_jitter records (train_dataset.jitter_records)."""
+    if not raw.is_cuda or raw.dtype != torch.uint8 or raw.dim() != 4 or raw.shape[3] != 3:
+        raise RuntimeError("image_pyramid_jitter: expected a CUDA uint8 tensor [V,Hs,Ws,3]")
+    raw = raw.contiguous()
+    v, hs, ws, _ = raw.shape
+    if not jitter.is_cuda or jitter.dtype != torch.uint8 or not jitter.is_contiguous() or jitter.numel() != v * JITTER_BYTES:
+        raise RuntimeError(f"image_pyramid_jitter: jitter must be a contiguous CUDA uint8 tensor of {v} x {JITTER_BYTES} bytes")
+    if jitter.data_ptr() % 4:
+        raise RuntimeError("image_pyramid_jitter: the jitter records must start on a 4-byte boundary (float / int32 fields)")
+    out = {"level_0": torch.empty((v, 3, height, width), device=raw.device, dtype=torch.float32)}
+    if all_levels:
+        for l in (1, 2, 3):
+            out[f"level_{l}"] = torch.empty((v, 3, height >> l, width >> l), device=raw.device, dtype=torch.float32)
+    lsum = torch.empty((v,), device=raw.device, dtype=torch.int64)
+    check(_lib.load().itermvs_image_pyramid_jitter(raw.data_ptr(), v, hs, ws, height, width, jitter.data_ptr(), lsum.data_ptr(),
+                                                   out["level_0"].data_ptr(), _ptr(out.get("level_1")), _ptr(out.get("level_2")),
+                                                   _ptr(out.get("level_3")), _stream()),
+          "itermvs_image_pyramid_jitter")
+    return out
+
+
+def gt_pyramid(depth_rows: Tensor, mask_src: Optional[Tensor], params: Tensor, height: int, width: int, recipe: int,
+               levels: Sequence[int] = (0, 1, 2, 3)) -> Tuple[Dict[str, Tensor], Dict[str, Tensor]]:
+    """itermvs_gt_pyramid: datasets/dtu_yao.py:80-119 (recipe _lib.GT_DTU) or blendedmvs.py:62-83 (_lib.GT_BLENDEDMVS) for a
+    batch.  depth_rows [B,Hs,Ws] float32 PFM payload (rows bottom-up), mask_src [B,Hs,Ws] uint8 depth_visual (DTU) or None,
+    params [B,4] float32 (device) -> ({'level_l': [B,1,H>>l,W>>l]} depth, same for the mask) for l in ``levels``"""
+    if not depth_rows.is_cuda or depth_rows.dtype != torch.float32 or depth_rows.dim() != 3 or not depth_rows.is_contiguous():
+        raise RuntimeError("gt_pyramid: depth_rows must be a contiguous CUDA float32 tensor [B,Hs,Ws]")
+    b, hs, ws = depth_rows.shape
+    if mask_src is not None and (not mask_src.is_cuda or mask_src.dtype != torch.uint8 or tuple(mask_src.shape) != (b, hs, ws)
+                                 or not mask_src.is_contiguous()):
+        raise RuntimeError("gt_pyramid: mask_src must be a contiguous CUDA uint8 tensor [B,Hs,Ws]")
+    if not params.is_cuda or params.dtype != torch.float32 or tuple(params.shape) != (b, 4) or not params.is_contiguous():
+        raise RuntimeError("gt_pyramid: params must be a contiguous CUDA float32 tensor [B,4]")
+    dev = depth_rows.device
+    depth = {f"level_{l}": torch.empty((b, 1, height >> l, width >> l), device=dev, dtype=torch.float32) for l in levels}
+    mask = {f"level_{l}": torch.empty((b, 1, height >> l, width >> l), device=dev, dtype=torch.float32) for l in levels}
+    check(_lib.load().itermvs_gt_pyramid(depth_rows.data_ptr(), _ptr(mask_src), params.data_ptr(), b, hs, ws, height, width, recipe,
+                                         *[_ptr(depth.get(f"level_{l}")) for l in range(4)],
+                                         *[_ptr(mask.get(f"level_{l}")) for l in range(4)], _stream()),
+          "itermvs_gt_pyramid")
+    return depth, mask
+
+
 _PROFILE_MASK = [0x3]
 
 

@@ -166,6 +166,12 @@ class Prefetcher:
                 break
         self.thread.join(timeout=5)
 
+    def _to_device(self, s):
+        return to_device(s, self.dev)
+
+    def _device_tensors(self, tensors):
+        return list(tensors[0].values()) + list(tensors[1].values()) + [tensors[2], tensors[3]]
+
     _PENDING = object()      # _stage(block=False): nothing decoded yet
 
     def _stage(self, block: bool = True):
@@ -187,7 +193,7 @@ class Prefetcher:
         if isinstance(s, Exception):
             raise s
         with torch.cuda.stream(self.stream):
-            tensors = to_device(s, self.dev)
+            tensors = self._to_device(s)
             ready = torch.cuda.Event()
             ready.record(self.stream)
         return s, tensors, ready
@@ -208,7 +214,7 @@ class Prefetcher:
                 # wait on the side stream's event: a cross-stream wait in front of a depth map's launches measured +60..+150 us
                 # per map on MI355X (tools/transfer_lab.py), a host wait on a completed event costs nothing
                 ready.synchronize()
-                for t in list(tensors[0].values()) + list(tensors[1].values()) + [tensors[2], tensors[3]]:
+                for t in self._device_tensors(tensors):
                     t.record_stream(cur)           # allocated on the side stream, used on this one
                 yield s, tensors
                 if nxt is self._PENDING:

@@ -4,8 +4,9 @@
 Same flags and constants (Adam lr 1e-3, MultiStepLR milestones 4,8,12 with gamma 1/2, gradient clip 2.0,
 checkpoint ``{'epoch','model','optimizer'}`` with ``module.``-prefixed keys per epoch), but one process
 per GPU with a single flat gradient all-reduce over RCCL (itermvs_amd/ddp.py) instead of
-``nn.DataParallel``.  Data: ``--dataset synthetic`` (photo-consistent planes with exact depth) or
-``module:Class`` yielding the reference's training sample dict (datasets/dtu_yao.py:227-232).
+``nn.DataParallel``.  Data: ``--dataset synthetic`` (photo-consistent planes with exact depth), ``dtu_yao`` or
+``blendedmvs`` (the reference's two training sets, itermvs_amd/train_dataset.py: decoded on a few host threads, jitter,
+normalisation, pyramids and ground truth on the GPU).
 """
 from __future__ import annotations
 
@@ -31,7 +32,7 @@ LR_GAMMA = 0.5             # train.py:124-127 ("lrepochs 4,8,12:2")
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="IterMVS training (MI355X)")
     p.add_argument("--mode", default="train", choices=["train", "val"])
-    p.add_argument("--dataset", default="synthetic")
+    p.add_argument("--dataset", default="synthetic", choices=["synthetic", "dtu_yao", "blendedmvs"])
     p.add_argument("--trainpath"); p.add_argument("--valpath"); p.add_argument("--trainlist"); p.add_argument("--vallist")
     p.add_argument("--epochs", type=int, default=16)
     p.add_argument("--lr", type=float, default=0.001)
@@ -48,8 +49,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--iteration", type=int, default=4)
     p.add_argument("--n_views", type=int, default=5)
-    p.add_argument("--img_wh", nargs="+", type=int, default=[640, 512])
-    p.add_argument("--steps_per_epoch", type=int, default=8, help="synthetic dataset only")
+    p.add_argument("--img_wh", nargs="+", type=int, default=None, help="default 640 512 (blendedmvs: 768 576; see image_size)")
+    p.add_argument("--steps_per_epoch", type=int, default=None,
+                   help="synthetic: steps per epoch (default 8); dtu_yao / blendedmvs: a cap on the steps of an epoch")
+    p.add_argument("--num_workers", type=int, default=4, help="decode threads of the training input side (train.py:89)")
     p.add_argument("--graph", action="store_true",
                    help="replay the whole step (forward, loss, backward, all-reduce, clip, Adam) as ONE hipGraph after three eager "
                         "warm-up steps (itermvs_amd.train_step.CapturedTrainStep): the eager step is launch-bound")
@@ -57,6 +60,40 @@ def build_parser() -> argparse.ArgumentParser:
                    help="storage type of the feature pyramids the fused correlation kernels gather from (BASELINE cfg 4: bf16); "
                         "arithmetic, gradients and weights stay fp32")
     return p
+
+
+def resolve_args(parser: argparse.ArgumentParser, args: argparse.Namespace) -> argparse.Namespace:
+    """defaults that depend on the dataset (train.py:62-63: valpath defaults to trainpath); a real dataset needs its paths"""
+    args.img_wh = image_size(args)
+    if args.dataset != "synthetic":
+        if args.valpath is None:
+            args.valpath = args.trainpath
+        need = ["trainpath", "trainlist"] if args.mode == "train" else []
+        need += ["vallist"]
+        for name in need:
+            if getattr(args, name) is None:
+                parser.error(f"--dataset {args.dataset} needs --{name}")
+        if args.mode == "val" and args.valpath is None:
+            parser.error(f"--dataset {args.dataset} needs --valpath (or --trainpath)")
+    return args
+
+
+def image_size(args):
+    """--img_wh, or its default for the dataset (also for parsed arguments that did not go through resolve_args)"""
+    if args.img_wh is not None:
+        return list(args.img_wh)
+    return [768, 576] if getattr(args, "dataset", "synthetic") == "blendedmvs" else [640, 512]
+
+
+def synthetic_steps(args) -> int:
+    return 8 if args.steps_per_epoch is None else args.steps_per_epoch
+
+
+def make_dataset(args, mode: str):
+    """train.py:86-87: the training set in train mode (robust_train, jitter), the validation set in val mode"""
+    from itermvs_amd.train_dataset import DATASETS
+    path, lst = (args.trainpath, args.trainlist) if mode == "train" else (args.valpath, args.vallist)
+    return DATASETS[args.dataset](path, lst, mode, args.n_views, tuple(image_size(args)), seed=args.seed)
 
 
 def parse_lrepochs(spec: str):
@@ -71,7 +108,7 @@ def synthetic_batch(args, step: int, rank: int, dev, world: int = 1):
     # world * batch_size * 131 leaves that range from world * batch_size >= 4 on -- wrap (the slots of a batch add < 4096)
     seed = (((step * world + rank) * args.batch_size) * 131) % (2 ** 32 - 4096)
     imgs, projs, dmin, dmax, gt, mask = synthetic.make_training_batch(
-        args.batch_size, num_views=args.n_views, height=args.img_wh[1], width=args.img_wh[0], seed=seed)
+        args.batch_size, num_views=args.n_views, height=image_size(args)[1], width=image_size(args)[0], seed=seed)
     to = lambda d: {k: v.to(dev) for k, v in d.items()}  # noqa: E731
     return to(imgs), to(projs), dmin.to(dev), dmax.to(dev), to(gt), to(mask)
 
@@ -166,16 +203,45 @@ def val_step(model, batch, regress: bool, iteration: int):
     return scalars
 
 
-def validate(model, args, rank: int, world: int, dev) -> dict:
+def validation_batches(args, rank: int, world: int, dev, dataset=None):
+    """(step, count, batch) of this rank's validation share: synthetic steps, or the dataset sharded without shuffle"""
+    if dataset is None:
+        n = synthetic_steps(args)
+        for step in range(n):
+            yield step, n, synthetic_batch(args, 10_000_019 + step, rank, dev, world)
+        return
+    from itermvs_amd.train_dataset import TrainPrefetcher, epoch_batches
+    batches = epoch_batches(len(dataset), args.batch_size, world, rank, args.seed, 0, train=False, max_steps=args.steps_per_epoch)
+    for step, (_, batch) in enumerate(TrainPrefetcher(dataset, batches, dev, args.num_workers)):
+        yield step, len(batches), batch
+
+
+def val_keys(iteration: int):
+    """the scalars val_step returns, sorted"""
+    keys = ["loss", "abs_error_initial", "thres1mm_initial", "abs_error_final_full"] + [f"thres{t}mm_final_full" for t in (1, 2, 4, 8)]
+    keys += [f"{m}_gru_{j}" for j in range(1, iteration + 1) for m in ("thres1mm", "abs_error")]
+    return sorted(keys)
+
+
+def validate(model, args, rank: int, world: int, dev, dataset=None) -> dict:
     """train.py:177-190 (test): every rank scores its share of the validation steps; the means are averaged over ranks"""
     total, n = {}, 0
-    for step in range(args.steps_per_epoch):
-        sc = val_step(model, synthetic_batch(args, 10_000_019 + step, rank, dev, world), args.regress, args.iteration)
+    for step, steps, batch in validation_batches(args, rank, world, dev, dataset):
+        sc = val_step(model, batch, args.regress, args.iteration)
         for k, v in sc.items():
             total[k] = total.get(k, 0.0) + v
         n += 1
         if rank == 0:
-            print("Iter {}/{}, test loss = {:.3f}".format(step, args.steps_per_epoch, sc["loss"]))
+            print("Iter {}/{}, test loss = {:.3f}".format(step, steps, sc["loss"]))
+    if dataset is not None:
+        # the round-robin shard can leave ranks with one batch fewer, or none: reduce the fixed set of sums and the batch
+        # counts, so every rank sends a tensor of the same size and the mean is over batches (DictAverageMeter)
+        keys = val_keys(args.iteration)
+        assert not total or set(total) == set(keys), sorted(set(total) ^ set(keys))
+        t = torch.tensor([total.get(k, 0.0) for k in keys] + [float(n)], device=dev, dtype=torch.float64)
+        if world > 1:
+            torch.distributed.all_reduce(t)
+        return dict(zip(keys, (t[:-1] / max(float(t[-1]), 1.0)).tolist()))
     keys = sorted(total)
     t = torch.tensor([total[k] / max(n, 1) for k in keys], device=dev, dtype=torch.float64)
     if world > 1:
@@ -184,8 +250,23 @@ def validate(model, args, rank: int, world: int, dev) -> dict:
     return dict(zip(keys, t.tolist()))
 
 
+def training_batches(args, epoch: int, rank: int, world: int, dev, dataset=None):
+    """(step, count, batch) of one training epoch on this rank: synthetic steps, or the dataset's shuffled shard
+    (train.py:89: shuffle, drop_last) through the GPU input side"""
+    if dataset is None:
+        n = synthetic_steps(args)
+        for step in range(n):
+            yield step, n, synthetic_batch(args, epoch * n + step, rank, dev, world)
+        return
+    from itermvs_amd.train_dataset import TrainPrefetcher, epoch_batches
+    batches = epoch_batches(len(dataset), args.batch_size, world, rank, args.seed, epoch, train=True, max_steps=args.steps_per_epoch)
+    for step, (_, batch) in enumerate(TrainPrefetcher(dataset, batches, dev, args.num_workers, epoch=epoch)):
+        yield step, len(batches), batch
+
+
 def main() -> None:
-    args = build_parser().parse_args()
+    parser = build_parser()
+    args = resolve_args(parser, parser.parse_args())
     rank, local_rank, world = shard.init_distributed()
     torch.manual_seed(args.seed)
     torch.cuda.set_device(local_rank)
@@ -208,10 +289,11 @@ def main() -> None:
     ddp.broadcast_parameters(model)
     milestones, gamma = parse_lrepochs(args.lrepochs)
     sched = torch.optim.lr_scheduler.MultiStepLR(optimizer, milestones, gamma=gamma, last_epoch=start_epoch - 1)
-    if args.dataset != "synthetic":
-        raise SystemExit("only --dataset synthetic is built in; plug a dataset module in via itermvs_amd")
+    real = args.dataset != "synthetic"
+    val_set = make_dataset(args, "val") if real else None
+    train_set = make_dataset(args, "train") if real and args.mode == "train" else None
     if args.mode == "val":                                                               # train.py:297-300
-        means = validate(model, args, rank, world, dev)
+        means = validate(model, args, rank, world, dev, val_set)
         if rank == 0:
             print("final", means)
         shard.barrier()
@@ -221,9 +303,8 @@ def main() -> None:
         from itermvs_amd.train_step import CapturedTrainStep
         captured = CapturedTrainStep(model, optimizer, args.regress, clip=GRAD_CLIP)
     for epoch in range(start_epoch, args.epochs):
-        for step in range(args.steps_per_epoch):
+        for step, steps, batch in training_batches(args, epoch, rank, world, dev, train_set):
             t0 = time.time()
-            batch = synthetic_batch(args, epoch * args.steps_per_epoch + step, rank, dev, world)
             if captured is not None:
                 loss, err = (float(t) for t in captured.step(batch))
                 captured.check()
@@ -231,11 +312,11 @@ def main() -> None:
                 loss, err = train_step(model, optimizer, batch, args.regress)
             if rank == 0 and step % args.summary_freq == 0:
                 print("Epoch {}/{}, Iter {}/{}, train loss = {:.3f}, abs depth error = {:.3f} mm, time = {:.3f}".format(
-                    epoch, args.epochs, step, args.steps_per_epoch, loss, err, time.time() - t0))
+                    epoch, args.epochs, step, steps, loss, err, time.time() - t0))
         sched.step()
         if rank == 0 and (epoch + 1) % args.save_freq == 0:
             save_checkpoint("{}/model_{:0>6}.ckpt".format(args.logdir, epoch), epoch, model, optimizer)
-        means = validate(model, args, rank, world, dev)                                   # train.py:160-175
+        means = validate(model, args, rank, world, dev, val_set)                          # train.py:160-175
         if captured is not None:
             captured.check()                       # a projection flagged by a validation forward belongs to THIS phase
         if rank == 0:
