@@ -648,7 +648,36 @@ int itermvs_fuse_points(const double* depth_avg, const uint8_t* final_mask, cons
                         uint32_t* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * itermvs_image_pyramid -- the input side of the path: datasets/dtu_yao_eval.py:61-74
+ * The COLMAP converter's two device stages (csrc/colmap.hip; colmap_input.py of the reference, host side: itermvs_amd/colmap.py).
+ * Common inputs (device): the images' observation lists as CSR -- offsets [V+1] int64 ascending, point [offsets[V]] int32 = dense
+ *   point index into xyz or -1, in file order (image index = position in images.bin) -- and xyz [P][3] fp64.  An entry outside
+ *   [0, P) is ignored like -1.  Validation before launch: ITERMVS_ERR_NULL for a NULL pointer, ITERMVS_ERR_DIMS for V < 1 or
+ *   P < 1; that offsets ascend and end inside `point` is the caller's duty (itermvs_amd.ops checks it on the host).  Neither
+ *   entry point allocates or synchronises; one launch each.
+ *
+ * itermvs_view_scores -- calc_score and the pair loop (colmap_input.py:336-364).  centre [V][3] fp64 = -R^T t.  For i < j,
+ *   score[i][j] = score[j][i] = sum over the entries pid of image i's list (list order, WITH multiplicity, -1 skipped) that occur
+ *   in image j's list of exp(-(th - theta0)^2 / (2 s^2)), th = (180 / pi) acos(<ci - p, cj - p> / |ci - p| / |cj - p|) in degrees,
+ *   s = sigma1 if th <= theta0 else sigma2.  score [V][V] fp64: EVERY element is written (diagonal 0, pairs without a common
+ *   point exactly 0, bitwise symmetric).  All arithmetic fp64 without fused multiply-add.  Each pair is summed by one wave in a
+ *   fixed shape (lane t takes entries t, t + 64, ..; a fixed shuffle tree), without floating-point atomics: two runs on the same
+ *   input give the same bits.  Membership is a bitmap of image j's points in LDS, 524288 points per chunk; larger P is walked
+ *   chunk by chunk and the chunks' sums are added in ascending order.
+ *   Unlike the reference the cosine is clamped to [-1, 1] (np.arccos returns NaN for a cosine that rounded above 1).
+ *
+ * itermvs_depth_ranges -- colmap_input.py:319-333.  ext_row2 [V][4] fp64 = row 2 of each extrinsic.  With
+ *   zs = sorted(((e0 x + e1 y) + e2 z) + e3 over the image's valid observations, a repeated point counting twice; no FMA):
+ *   range[v] = {zs[int(len * .01)], zs[int(len * .99)]}: exact order statistics (8-pass radix select; the result is one of the
+ *   z values bit for bit), no interpolation.  range [V][2] fp64.  An image without a valid observation gets {NaN, NaN} (the
+ *   reference raises IndexError at :330; the host raises ValueError).
+ * ------------------------------------------------------------------------------------------ */
+int itermvs_view_scores(const int64_t* offsets, const int32_t* point, const double* xyz, const double* centre, int32_t V,
+                        int32_t P, double theta0, double sigma1, double sigma2, double* score, void* stream);
+int itermvs_depth_ranges(const int64_t* offsets, const int32_t* point, const double* xyz, const double* ext_row2, int32_t V,
+                         int32_t P, double* range, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * itermvs_image_pyramid --the input side of the path: datasets/dtu_yao_eval.py:61-74
  * (read_img) on the GPU.  src [V,Hs,Ws,3] uint8 interleaved RGB (the decoded images of one sample, same size) ->
  *   level0 [V,3,H,W]       = cv2.resize(2 * src / 255. - 1, (W, H), INTER_LINEAR)   (float32)
  *   level1..3 [V,3,H>>l,W>>l] = cv2.resize(level0, ..., INTER_LINEAR)               (may be NULL: the network reads level 0 only)

@@ -1374,6 +1374,52 @@ def fuse_points(depth_avg: Tensor, final_mask: Tensor, cam: Tensor, rgb: Tensor,
           "itermvs_fuse_points")
 
 
+def _colmap_inputs(what: str, offsets: Tensor, point: Tensor, xyz: Tensor, per_view: Tensor, width: int) -> Tuple[int, int]:
+    """shared checks of view_scores / depth_ranges -> (V, P).  ``offsets`` is the one HOST tensor: its values are checked here
+    (ascending from offsets[0] >= 0 to offsets[V] <= len(point)), which the kernels rely on for their reads of ``point``."""
+    for t, name in ((point, "point"), (xyz, "xyz"), (per_view, "per-view matrix")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{what}: {name}: expected a CUDA/ROCm tensor - the IterMVS HIP engine has no CPU path")
+    if not isinstance(offsets, torch.Tensor) or offsets.is_cuda or offsets.dtype != torch.int64 or offsets.dim() != 1:
+        raise RuntimeError(f"{what}: offsets must be a 1-D int64 HOST tensor (it is validated here and uploaded)")
+    v = offsets.numel() - 1
+    if point.dtype != torch.int32 or point.dim() != 1 or not point.is_contiguous():
+        raise RuntimeError(f"{what}: point must be a contiguous 1-D int32 tensor")
+    if xyz.dtype != torch.float64 or xyz.dim() != 2 or xyz.shape[1] != 3 or not xyz.is_contiguous():
+        raise RuntimeError(f"{what}: xyz must be a contiguous float64 [P,3] tensor")
+    if per_view.dtype != torch.float64 or tuple(per_view.shape) != (v, width) or not per_view.is_contiguous():
+        raise RuntimeError(f"{what}: expected a contiguous float64 [{v},{width}] per-view tensor, got {tuple(per_view.shape)}")
+    if v >= 1 and (int(offsets[0]) < 0 or int(offsets[-1]) > point.numel() or bool((offsets[1:] < offsets[:-1]).any())):
+        raise RuntimeError(f"{what}: offsets must ascend from >= 0 to <= len(point) = {point.numel()}")
+    return v, int(xyz.shape[0])
+
+
+def view_scores(offsets: Tensor, point: Tensor, xyz: Tensor, centre: Tensor, theta0: float = 5.0, sigma1: float = 1.0,
+                sigma2: float = 10.0, offsets_dev: Optional[Tensor] = None) -> Tensor:
+    """itermvs_view_scores (colmap_input.py:336-364): the symmetric float64 [V,V] view-selection score matrix.  offsets: HOST
+    int64 [V+1] (CSR of the observation lists), point int32 [total] (dense point index or -1), xyz float64 [P,3], centre
+    float64 [V,3] on the device; ``offsets_dev``: a device copy of ``offsets`` the caller already holds (uploaded here otherwise).
+    Nothing is read back and nothing synchronises."""
+    v, p = _colmap_inputs("view_scores", offsets, point, xyz, centre, 3)
+    score = torch.empty((max(v, 0), max(v, 0)), device=point.device, dtype=torch.float64)
+    off = offsets.to(point.device) if offsets_dev is None else offsets_dev
+    check(_lib.load().itermvs_view_scores(off.data_ptr(), point.data_ptr(), xyz.data_ptr(), centre.data_ptr(), v, p, float(theta0),
+                                          float(sigma1), float(sigma2), score.data_ptr(), _stream()), "itermvs_view_scores")
+    return score
+
+
+def depth_ranges(offsets: Tensor, point: Tensor, xyz: Tensor, ext_row2: Tensor, offsets_dev: Optional[Tensor] = None) -> Tensor:
+    """itermvs_depth_ranges (colmap_input.py:319-333): float64 [V,2] = the order statistics int(len * .01) and int(len * .99)
+    of every image's observation depths; NaN for an image without a valid observation.  ext_row2 float64 [V,4] = row 2 of the
+    extrinsics; the other arguments as :func:`view_scores`."""
+    v, p = _colmap_inputs("depth_ranges", offsets, point, xyz, ext_row2, 4)
+    out = torch.empty((max(v, 0), 2), device=point.device, dtype=torch.float64)
+    off = offsets.to(point.device) if offsets_dev is None else offsets_dev
+    check(_lib.load().itermvs_depth_ranges(off.data_ptr(), point.data_ptr(), xyz.data_ptr(), ext_row2.data_ptr(), v, p,
+                                           out.data_ptr(), _stream()), "itermvs_depth_ranges")
+    return out
+
+
 CORRNET_WEIGHT_FLOATS = 14288
 CORRNET_WEIGHT_FLOATS_SPLIT3 = 23120     # bf16x3 form: conv0 + conv2 + the two transposed convolutions as split bf16 operands
 
