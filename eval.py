@@ -71,6 +71,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--geo_pixel_thres", type=float, default=1)
     p.add_argument("--geo_depth_thres", type=float, default=0.01)
     p.add_argument("--photo_thres", type=float, default=0.3)
+    p.add_argument("--geo_mask_thres", type=int, default=3,
+                   help="--filter: source views that must agree with a reference pixel (eval.py:323-324: the reference fuses DTU "
+                        "with 4 and everything else with 3; the default 3 keeps this driver's clouds as they were)")
     p.add_argument("--num_samples", type=int, default=8, help="synthetic dataset: number of reference views")
     p.add_argument("--filter", action="store_true", help="fuse the saved depth maps of every scan into a point cloud (eval.py:311-325)")
     p.add_argument("--fuse_points", default="host", choices=["host", "device"],
@@ -271,7 +274,8 @@ def fuse_scans(args) -> int:
         scan = scans[i]
         stats = fusion.filter_depth(os.path.join(args.testpath, scan), os.path.join(args.outdir, scan),
                                     os.path.join(args.outdir, scan + ".ply"), args.geo_pixel_thres, args.geo_depth_thres,
-                                    args.photo_thres, device=dev, img_wh=tuple(args.img_wh), points=args.fuse_points,
+                                    args.photo_thres, geo_mask_thres=args.geo_mask_thres, device=dev, img_wh=tuple(args.img_wh),
+                                    points=args.fuse_points,
                                     save_masks=args.save_masks)
         for v, (g, ph, f) in stats.items():
             print("processing {}, ref-view{:0>2}, geo_mask:{:3f} photo_mask:{:3f} final_mask: {:3f}".format(scan, v, g, ph, f))

@@ -677,6 +677,55 @@ int itermvs_depth_ranges(const int64_t* offsets, const int32_t* point, const dou
                          int32_t P, double* range, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The searches of the DTU point-cloud evaluation (csrc/cloud_eval.hip; the .m scripts under evaluations/dtu of the reference, host side:
+ * itermvs_amd/cloud_eval.py).  Clouds are float32 [n][3] (PLY coordinates); all arithmetic is fp64 on them, the squared distance
+ * is ((dx*dx) + (dy*dy)) + (dz*dz) without contraction and the distance its IEEE sqrt.
+ * The neighbour structure is a uniform grid (origin ox, oy, oz; nx, ny, nz cells of edge `edge`): cell = floor((p - origin) / edge),
+ * key = (cx * ny + cy) * nz + cz.  Validation before any launch, common to all: ITERMVS_ERR_NULL for a NULL pointer;
+ * ITERMVS_ERR_DIMS for a point count < 1 or > 0x7fffff00, a non-finite origin, edge <= 0, or a grid dimension outside
+ * 1 .. 2^21 (a cloud whose extent does not fit the 63-bit key).  No entry point allocates or synchronises; one launch each.
+ * No content of a cloud (NaN, Inf, huge coordinates) makes a kernel read or write outside its buffers.
+ *
+ * itermvs_cloud_cell_keys: keys[i] = the key of point i; INT64_MAX for a point that is not finite or lies outside the grid.  The
+ *   caller sorts by key (the sorted arrays below are the points / keys / ranks in that order).
+ *
+ * itermvs_cloud_reduce_round -- one round of reducePts_haa.m:24-30 (the loop `if indexSet(id), indexSet(idx{i}) = 0,
+ *   indexSet(id) = 1` over rangesearch(..., dst), d2 <= dst*dst inclusive).  rank_sorted[i] = position of point i in the
+ *   visiting order (RandOrd).  state [n] int32, zeroed by the caller before the first round: 0 undecided, 1 kept, 2 removed.
+ *   An undecided point becomes removed if a neighbour of lower rank is kept, kept if no neighbour of lower rank is undecided;
+ *   *undecided (device int32, zeroed by the caller) is incremented for every point the round leaves undecided.  Repeating the
+ *   round until that count is 0 gives exactly the sequential loop's indexSet for the same order, in at most n rounds.
+ *   Needs edge >= dst (ITERMVS_ERR_DIMS otherwise, or for dst <= 0): the 27 cells around a point must hold the radius.
+ *
+ * itermvs_cloud_nn_distance -- MaxDistCP.m.  region (HOST memory) = {lo[3], hi[3]}: the queries the script's blocks cover,
+ *   lo[a] <= x < hi[a] with lo = BB(1,:), hi = (BB(1,:) + floor((BB(2,:) - BB(1,:)) / cap) * cap) + cap.  Queries: q_from [nq][3],
+ *   all of them or, with index != NULL, the n_index entries of index (int64, entries outside [0, nq) are skipped).  Targets:
+ *   to_sorted [nt][3] with keys_sorted on the given grid.  Per query, carried between calls on successively coarser grids:
+ *   best_d2 (fp64, +Inf before the first call), done (uint8, 0 before the first call; a done query is skipped).  A call searches
+ *   the rings 0 .. rings - 1 of cells around the query's cell, stops as soon as best_d2 <= ((r - 1) * edge * (1 - 2^-20))^2 or
+ *   that bound >= cap, and sets done when it stopped that way.  dist = min(sqrt(best_d2), cap); cap (and done) at once for a
+ *   query outside the region.  When done is set, dist = min(distance to the nearest target, cap) over ALL targets on the grid.
+ *   Unlike MaxDistCP.m, which returns the distance to the nearest point of the block enlarged by cap (possibly > cap: every
+ *   consumer discards >= 20), and without the one-ulp seams between neighbouring blocks' Low / High.
+ *   ITERMVS_ERR_DIMS also for cap <= 0, rings outside 1 .. 2^21, n_index outside 1 .. nq.
+ *
+ * itermvs_cloud_in_mask -- PointCompareMain.m:32-41.  out[i] = 1 iff v = round(((p - b) / res) + 1) (half away from zero, per
+ *   axis) lies in 1 .. (sx, sy, sz) and mask[vx - 1][vy - 1][vz - 1] != 0; mask is uint8 [sx][sy][sz] contiguous.
+ *   ITERMVS_ERR_DIMS for a size < 1, res <= 0 or a non-finite b / res.
+ * ------------------------------------------------------------------------------------------ */
+int itermvs_cloud_cell_keys(const float* xyz, int64_t n, double ox, double oy, double oz, int32_t nx, int32_t ny, int32_t nz,
+                            double edge, int64_t* keys, void* stream);
+int itermvs_cloud_reduce_round(const float* xyz_sorted, const int64_t* keys_sorted, const int32_t* rank_sorted, int64_t n,
+                               double ox, double oy, double oz, int32_t nx, int32_t ny, int32_t nz, double edge, double dst,
+                               int32_t* state, int32_t* undecided, void* stream);
+int itermvs_cloud_nn_distance(const float* q_from, int64_t nq, const int64_t* index, int64_t n_index, const float* to_sorted,
+                              const int64_t* keys_sorted, int64_t nt, double ox, double oy, double oz, int32_t nx, int32_t ny,
+                              int32_t nz, double edge, const double* region, double cap, int32_t rings, double* best_d2,
+                              uint8_t* done, double* dist, void* stream);
+int itermvs_cloud_in_mask(const float* xyz, int64_t n, const uint8_t* mask, int32_t sx, int32_t sy, int32_t sz, double bx,
+                          double by, double bz, double res, uint8_t* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * itermvs_image_pyramid --the input side of the path: datasets/dtu_yao_eval.py:61-74
  * (read_img) on the GPU.  src [V,Hs,Ws,3] uint8 interleaved RGB (the decoded images of one sample, same size) ->
  *   level0 [V,3,H,W]       = cv2.resize(2 * src / 255. - 1, (W, H), INTER_LINEAR)   (float32)

@@ -181,6 +181,15 @@ PROTOTYPES = {
     "itermvs_view_scores": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p,
                                       C.c_void_p]),
     "itermvs_depth_ranges": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "itermvs_cloud_cell_keys": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_double] * 3 + [C.c_int32] * 3 + [C.c_double, C.c_void_p,
+                                          C.c_void_p]),
+    "itermvs_cloud_reduce_round": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_double] * 3 + [C.c_int32] * 3 +
+                                   [C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "itermvs_cloud_nn_distance": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64] +
+                                  [C.c_double] * 3 + [C.c_int32] * 3 + [C.c_double, C.POINTER(C.c_double), C.c_double, C.c_int32,
+                                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "itermvs_cloud_in_mask": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p] + [C.c_int32] * 3 + [C.c_double] * 4 +
+                              [C.c_void_p, C.c_void_p]),
     "itermvs_profile_graph_count": (C.c_int, []),
     "itermvs_profile_graph_read": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "itermvs_profile_collect": (C.c_int, [C.POINTER(C.c_int32), c_float_p, C.c_int32]),

@@ -47,3 +47,66 @@ def read_pfm(filename: str) -> Tuple[np.ndarray, float]:
         endian = "<" if scale < 0 else ">"
         data = np.fromfile(f, endian + "f4")
     return np.flipud(data.reshape(height, width, channels)).copy(), abs(scale)
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def read_ply_xyz(filename: str) -> np.ndarray:
+    """vertex x, y, z of a PLY file as float32 [N,3]: ``ascii`` and ``binary_little_endian``, any further scalar vertex
+    properties (normals, colours: DTU's ``stl###_total.ply``, this project's 15-byte records) and any elements after the
+    vertices (faces).  Big-endian files, list properties inside the vertex element, an element in front of the vertices and a
+    short file raise a ValueError naming the file."""
+    def bad(why: str) -> ValueError:
+        return ValueError(f"{filename}: {why}")
+
+    with open(filename, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise bad("not a PLY file")
+        fmt, elements, props, current = None, [], [], None
+        while True:
+            raw = f.readline()
+            if not raw:
+                raise bad("PLY header without end_header")
+            words = raw.decode("ascii", "replace").split()
+            if not words or words[0] in ("comment", "obj_info"):
+                continue
+            if words[0] == "end_header":
+                break
+            if words[0] == "format" and len(words) >= 2:
+                fmt = words[1]
+            elif words[0] == "element" and len(words) == 3:
+                current = words[1]
+                elements.append((current, int(words[2])))
+            elif words[0] == "property" and current == "vertex":
+                if words[1] == "list":
+                    raise bad("list property inside the vertex element")
+                if len(words) != 3 or words[1] not in _PLY_TYPES:
+                    raise bad(f"unknown vertex property {' '.join(words[1:])!r}")
+                props.append((words[2], _PLY_TYPES[words[1]]))
+        if fmt not in ("ascii", "binary_little_endian"):
+            raise bad(f"format {fmt!r} is not supported (ascii and binary_little_endian are)")
+        if not elements or elements[0][0] != "vertex":
+            raise bad("the first element must be the vertices")
+        n = elements[0][1]
+        names = [p[0] for p in props]
+        if len(set(names)) != len(names) or any(a not in names for a in "xyz"):
+            raise bad(f"the vertex element needs x, y and z once each, has {names}")
+        if fmt == "ascii":
+            cols = [names.index(a) for a in "xyz"]
+            out = np.empty((n, 3), dtype=np.float32)
+            for i in range(n):
+                words = f.readline().split()
+                if len(words) < len(names):
+                    raise bad(f"vertex {i} of {n}: the file is short")
+                try:
+                    out[i] = [float(words[c]) for c in cols]
+                except ValueError:
+                    raise bad(f"vertex {i}: not a number") from None
+            return out
+        dtype = np.dtype([(name, "<" + t) for name, t in props])
+        data = np.fromfile(f, dtype=dtype, count=n)
+        if data.shape[0] != n:
+            raise bad(f"{data.shape[0]} of {n} vertices: the file is short")
+    return np.stack([data["x"].astype(np.float32), data["y"].astype(np.float32), data["z"].astype(np.float32)], 1)

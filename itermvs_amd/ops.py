@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -1417,6 +1417,90 @@ def depth_ranges(offsets: Tensor, point: Tensor, xyz: Tensor, ext_row2: Tensor, 
     off = offsets.to(point.device) if offsets_dev is None else offsets_dev
     check(_lib.load().itermvs_depth_ranges(off.data_ptr(), point.data_ptr(), xyz.data_ptr(), ext_row2.data_ptr(), v, p,
                                            out.data_ptr(), _stream()), "itermvs_depth_ranges")
+    return out
+
+
+class CloudGrid(NamedTuple):
+    """the uniform grid of the cloud_* searches: cell = floor((p - origin) / edge), key = (cx * ny + cy) * nz + cz"""
+    origin: Tuple[float, float, float]
+    dims: Tuple[int, int, int]
+    edge: float
+
+    def args(self) -> tuple:
+        return tuple(float(o) for o in self.origin) + tuple(int(d) for d in self.dims) + (float(self.edge),)
+
+
+def _cloud(what: str, t: Tensor, name: str, dtype=torch.float32, shape_tail: tuple = (3,)) -> Tensor:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{what}: {name}: expected a CUDA/ROCm tensor - the IterMVS HIP engine has no CPU path")
+    if t.dtype != dtype or tuple(t.shape[1:]) != shape_tail or t.dim() != 1 + len(shape_tail) or not t.is_contiguous():
+        raise RuntimeError(f"{what}: {name} must be a contiguous {dtype} [n{''.join(',%d' % s for s in shape_tail)}] tensor, "
+                           f"got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def cloud_cell_keys(xyz: Tensor, grid: CloudGrid) -> Tensor:
+    """itermvs_cloud_cell_keys: int64 [n] cell keys of float32 [n,3] points on ``grid``; INT64_MAX for a point that is not
+    finite or outside the grid.  An extent that does not fit the key (a dimension above 2^21) raises."""
+    _cloud("cloud_cell_keys", xyz, "xyz")
+    keys = torch.empty((xyz.shape[0],), device=xyz.device, dtype=torch.int64)
+    if xyz.shape[0]:
+        check(_lib.load().itermvs_cloud_cell_keys(xyz.data_ptr(), xyz.shape[0], *grid.args(), keys.data_ptr(), _stream()),
+              "itermvs_cloud_cell_keys")
+    return keys
+
+
+def cloud_reduce_round(xyz_sorted: Tensor, keys_sorted: Tensor, rank_sorted: Tensor, grid: CloudGrid, dst: float, state: Tensor,
+                       undecided: Tensor) -> None:
+    """itermvs_cloud_reduce_round: one round of the parallel form of reducePts_haa.m:24-30 over the key-sorted cloud.  state
+    int32 [n] (0 undecided, 1 kept, 2 removed) is updated in place; ``undecided`` (int32, one element, zeroed by the caller) counts
+    the points the round leaves undecided.  Nothing is read back."""
+    n = _cloud("cloud_reduce_round", xyz_sorted, "xyz_sorted").shape[0]
+    for t, dt, name, m in ((keys_sorted, torch.int64, "keys_sorted", n), (rank_sorted, torch.int32, "rank_sorted", n),
+                           (state, torch.int32, "state", n), (undecided, torch.int32, "undecided", 1)):
+        if _cloud("cloud_reduce_round", t, name, dt, ()).numel() != m:
+            raise RuntimeError(f"cloud_reduce_round: {name} must have {m} elements, got {t.numel()}")
+    check(_lib.load().itermvs_cloud_reduce_round(xyz_sorted.data_ptr(), keys_sorted.data_ptr(), rank_sorted.data_ptr(), n,
+                                                 *grid.args(), float(dst), state.data_ptr(), undecided.data_ptr(), _stream()),
+          "itermvs_cloud_reduce_round")
+
+
+def cloud_nn_distance(q_from: Tensor, to_sorted: Tensor, keys_sorted: Tensor, grid: CloudGrid, region: Sequence[float], cap: float,
+                      rings: int, best_d2: Tensor, done: Tensor, dist: Tensor, index: Optional[Tensor] = None) -> None:
+    """itermvs_cloud_nn_distance: one grid's rings of the capped nearest-neighbour search of MaxDistCP.m.  q_from float32 [nq,3];
+    to_sorted float32 [nt,3] / keys_sorted int64 [nt] in key order on ``grid``; region = the six floats lo[3], hi[3] of the
+    covered queries; best_d2 float64 [nq] (+Inf at first), done uint8 [nq] (0 at first) and dist float64 [nq] are updated in
+    place; ``index``: int64 list of the queries to look at (default: all).  Nothing is read back."""
+    nq = _cloud("cloud_nn_distance", q_from, "q_from").shape[0]
+    nt = _cloud("cloud_nn_distance", to_sorted, "to_sorted").shape[0]
+    for t, dt, name, m in ((keys_sorted, torch.int64, "keys_sorted", nt), (best_d2, torch.float64, "best_d2", nq),
+                           (done, torch.uint8, "done", nq), (dist, torch.float64, "dist", nq)):
+        if _cloud("cloud_nn_distance", t, name, dt, ()).numel() != m:
+            raise RuntimeError(f"cloud_nn_distance: {name} must have {m} elements, got {t.numel()}")
+    if index is not None:
+        _cloud("cloud_nn_distance", index, "index", torch.int64, ())
+    if len(region) != 6:
+        raise RuntimeError("cloud_nn_distance: region is lo[3] + hi[3]")
+    reg = (C.c_double * 6)(*[float(r) for r in region])
+    check(_lib.load().itermvs_cloud_nn_distance(q_from.data_ptr(), nq, _ptr(index), 0 if index is None else index.numel(),
+                                                to_sorted.data_ptr(), keys_sorted.data_ptr(), nt, *grid.args(), reg, float(cap),
+                                                int(rings), best_d2.data_ptr(), done.data_ptr(), dist.data_ptr(), _stream()),
+          "itermvs_cloud_nn_distance")
+
+
+def cloud_in_mask(xyz: Tensor, mask: Tensor, origin: Sequence[float], res: float) -> Tensor:
+    """itermvs_cloud_in_mask (PointCompareMain.m:32-41): uint8 [n] = the point's voxel round(((p - origin) / res) + 1) (half away
+    from zero) lies inside the uint8 [sx,sy,sz] ``mask`` and is set there."""
+    n = _cloud("cloud_in_mask", xyz, "xyz").shape[0]
+    if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
+        raise RuntimeError("cloud_in_mask: mask: expected a CUDA/ROCm tensor - the IterMVS HIP engine has no CPU path")
+    if mask.dtype != torch.uint8 or mask.dim() != 3 or not mask.is_contiguous():
+        raise RuntimeError(f"cloud_in_mask: mask must be a contiguous uint8 [sx,sy,sz] tensor, got {mask.dtype} {tuple(mask.shape)}")
+    out = torch.empty((n,), device=xyz.device, dtype=torch.uint8)
+    if n:
+        check(_lib.load().itermvs_cloud_in_mask(xyz.data_ptr(), n, mask.data_ptr(), *[int(s) for s in mask.shape],
+                                                *[float(o) for o in origin], float(res), out.data_ptr(), _stream()),
+              "itermvs_cloud_in_mask")
     return out
 
 
