@@ -726,6 +726,63 @@ int itermvs_cloud_in_mask(const float* xyz, int64_t n, const uint8_t* mask, int3
                           double by, double bz, double res, uint8_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The point-cloud passes of the Tanks and Temples evaluation (csrc/cloud_register.hip; host side: itermvs_amd/cloud_register.py).
+ * Additions compatible with ABI 18.  Clouds are float32 [n][3]; all arithmetic is fp64 on them without contraction.  T is a 4x4
+ * fp64 row-major matrix in HOST memory (rows 0..2 are used; identity = no transform), applied per row as
+ * ((m0*x + m1*y) + m2*z) + m3.  Every check precedes the first launch: ITERMVS_ERR_NULL for a NULL pointer, ITERMVS_ERR_DIMS for a
+ * point count < 1 or > 0x7fffff00, a non-finite T, and what each entry adds.  Nothing allocates or synchronises; no float atomics:
+ * the same input gives the same bytes on every run.
+ *
+ * itermvs_cloud_crop -- replaces Open3D's SelectionPolygonVolume.crop_point_cloud.  out[i] = 1 iff c = T * p_i lies in the volume:
+ *   axis w in {0, 1, 2} is the orthogonal axis, axis_min <= c_w <= axis_max (inclusive), and (c_u, c_v) is inside the polygon by
+ *   the even-odd rule, (u, v) = (1, 2) for w = 0 (X), (0, 2) for w = 1 (Y), (0, 1) for w = 2 (Z).  polygon: HOST memory, fp64
+ *   [n_poly][3] vertices (only u and v are read), 3 <= n_poly <= 1024.  With a = vertex k and b = vertex k + 1 (the last edge
+ *   closes the polygon), edge (a, b) toggles iff (a_v > c_v) != (b_v > c_v) and
+ *   c_u < (((b_u - a_u) * (c_v - a_v)) / (b_v - a_v)) + a_u, in exactly this order of operations.  A point whose c is not finite
+ *   is outside.  poly_ws: device scratch of 2 * n_poly doubles (the polygon travels there as kernel arguments, 128 vertices per
+ *   launch, before the crop launch on the same stream).  ITERMVS_ERR_DIMS also for an axis outside 0..2, n_poly outside 3..1024,
+ *   a NaN bound or a non-finite polygon coordinate.
+ *
+ * itermvs_cloud_voxel_heads / itermvs_cloud_voxel_mean -- replace Open3D's voxel_down_sample: one output point per occupied
+ *   voxel, the mean of its members.  The caller computes the keys with itermvs_cloud_cell_keys (origin = min_bound - voxel / 2,
+ *   edge = voxel) and sorts them STABLY.  voxel_heads: head[i] (int32) = 1 iff keys_sorted[i] != INT64_MAX and i is the first of
+ *   its run of equal keys.  The caller's inclusive prefix sum of head, minus 1, is rank (int64 [n]; torch.cumsum: plumbing), its
+ *   last element + 1 is n_out.  voxel_mean: the head of every run adds the run's coordinates in sorted order -- original index
+ *   order inside a voxel -- in fp64 starting from 0.0, divides by the count and rounds once to float32 into out[rank][3]; a rank
+ *   outside [0, n_out) writes nothing.  Output order: ascending voxel key (Open3D's is a hash map's).  Runs longer than 64 points
+ *   are summed by the whole wave from coalesced loads, in the same order and therefore to the same bits.
+ *   ITERMVS_ERR_DIMS also for n_out outside 1 .. n.
+ *
+ * itermvs_cloud_nn_index -- replaces the KD-tree correspondence search of Open3D's registration_icp.  For every query
+ *   T * q_i: the nearest target of to_sorted (key order on the given grid, keys_sorted as for itermvs_cloud_nn_distance) with
+ *   d2 < max_dist * max_dist.  The bound is EXCLUSIVE: a target exactly max_dist away is no match.  idx[i] = perm[position] (perm:
+ *   int64 [nt], the sorted position's index in the caller's unsorted target array) or -1; d2[i] = the squared distance (fp64) or
+ *   +Inf.  Ties on d2 go to the lowest perm value, whatever the traversal order.  The search walks the rings 0 .. rings - 1 with
+ *   the ring walk and stop bounds of itermvs_cloud_nn_distance (csrc/cloud_grid.hpp); rings >= the first ring whose lower bound
+ *   (r - 1) * edge * (1 - 2^-20) reaches max_dist makes the result exact.  nt = 0 is allowed (every query unmatched; the target
+ *   pointers may then be NULL).  ITERMVS_ERR_DIMS also for nt < 0, a bad grid, max_dist <= 0, rings outside 1 .. 2^21.
+ *
+ * itermvs_cloud_umeyama_sums -- replaces the sums inside Open3D's TransformationEstimationPointToPoint (Eigen::umeyama).  Over the
+ *   correspondences with 0 <= idx[i] < nt, p = T * q_i, t = target[idx[i]] (the UNSORTED targets): sums[18] = {count, sum p (3),
+ *   sum t (3), sum t p^T (9, row = t, column = p), sum ((px*px + py*py) + pz*pz), sum d2[i]}.  Fixed-shape reduction:
+ *   G = itermvs_cloud_umeyama_groups(n) = min(1024, ceil(n / 2048)) workgroups of 256 threads; workgroup g owns the slice
+ *   [g * S, (g + 1) * S), S = ceil(n / G); thread t adds elements t, t + 256, ... in order; lanes combine by xor-butterfly
+ *   (32, 16, ..., 1), the 4 waves in wave order -> partials[g][18] (device, G * 18 doubles); one workgroup adds the partials in
+ *   ascending g -> sums (device, 18 doubles).  ITERMVS_ERR_DIMS also for nt < 0.
+ * ------------------------------------------------------------------------------------------ */
+int itermvs_cloud_crop(const float* xyz, int64_t n, const double* T, int32_t axis, double axis_min, double axis_max,
+                       const double* polygon, int32_t n_poly, double* poly_ws, uint8_t* out, void* stream);
+int itermvs_cloud_voxel_heads(const int64_t* keys_sorted, int64_t n, int32_t* head, void* stream);
+int itermvs_cloud_voxel_mean(const float* xyz_sorted, const int64_t* keys_sorted, const int64_t* rank, int64_t n, int64_t n_out,
+                             float* out, void* stream);
+int itermvs_cloud_nn_index(const float* q, int64_t nq, const double* T, const float* to_sorted, const int64_t* keys_sorted,
+                           const int64_t* perm, int64_t nt, double ox, double oy, double oz, int32_t nx, int32_t ny, int32_t nz,
+                           double edge, double max_dist, int32_t rings, int64_t* idx, double* d2, void* stream);
+int itermvs_cloud_umeyama_groups(int64_t n);
+int itermvs_cloud_umeyama_sums(const float* q, int64_t n, const double* T, const int64_t* idx, const double* d2,
+                               const float* target, int64_t nt, double* partials, double* sums, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * itermvs_image_pyramid --the input side of the path: datasets/dtu_yao_eval.py:61-74
  * (read_img) on the GPU.  src [V,Hs,Ws,3] uint8 interleaved RGB (the decoded images of one sample, same size) ->
  *   level0 [V,3,H,W]       = cv2.resize(2 * src / 255. - 1, (W, H), INTER_LINEAR)   (float32)

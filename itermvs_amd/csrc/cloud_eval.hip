@@ -32,41 +32,9 @@
 //
 // itermvs_cloud_in_mask (PointCompareMain.m:32-41): v = round(((p - BB(1)) / Res) + 1) with C round() = MATLAB's round (half away
 // from zero), inside 1..size on all three axes, and ObsMask(v) set.
-#include <math.h>
-
-#include "common.hpp"
+#include "cloud_grid.hpp"
 
 namespace itermvs {
-
-constexpr int kCloudBlock = 256;
-constexpr int kMaxCellDim = 1 << 21;                    // per axis: three axes fit a 63-bit key
-constexpr double kCellClamp = 4194304.0;                // 2^22: a query's cell far outside the grid, still safe in int arithmetic
-constexpr double kRingShrink = 1.0 - 1.0 / 1048576.0;   // ring lower bounds give way 2^-20 to the rounding of (p - origin) / edge
-constexpr long long kNoKey = 0x7fffffffffffffffLL;
-
-struct CloudGrid {
-    double ox, oy, oz, edge;
-    int nx, ny, nz;
-};
-
-__device__ __forceinline__ double cell_of(double p, double o, double edge) {
-    return floor((p - o) / edge);
-}
-
-// first position in keys[0 : n) whose key is >= want; n < 2^31, so 32 halvings always finish
-__device__ __forceinline__ long long lower_bound(const long long* __restrict__ keys, long long n, long long want) {
-    long long lo = 0, hi = n;
-    for (int it = 0; it < 32 && lo < hi; ++it) {
-        const long long mid = lo + ((hi - lo) >> 1);
-        if (keys[mid] < want) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ double dist2(double qx, double qy, double qz, const float* __restrict__ p) {
-    const double dx = qx - (double)p[0], dy = qy - (double)p[1], dz = qz - (double)p[2];
-    return ((dx * dx) + (dy * dy)) + (dz * dz);
-}
 
 __global__ void __launch_bounds__(kCloudBlock) cloud_cell_keys_kernel(const float* __restrict__ xyz, long long n, CloudGrid g,
                                                                       long long* __restrict__ keys) {
@@ -124,21 +92,6 @@ struct CloudRegion {
     double lo[3], hi[3];
 };
 
-// the targets of the cells z0..z1 (clipped to the grid) of row (x, y)
-__device__ __forceinline__ double scan_cells(const float* __restrict__ t, const long long* __restrict__ keys, long long nt,
-                                             const CloudGrid& g, int x, int y, int z0, int z1, double qx, double qy, double qz,
-                                             double best) {
-    z0 = z0 < 0 ? 0 : z0;
-    z1 = z1 > g.nz - 1 ? g.nz - 1 : z1;
-    if (z0 > z1) return best;
-    const long long row = ((long long)x * g.ny + y) * g.nz, last = row + z1;
-    for (long long j = lower_bound(keys, nt, row + z0); j < nt && keys[j] <= last; ++j) {
-        const double d2 = dist2(qx, qy, qz, t + j * 3);
-        best = d2 < best ? d2 : best;                      // NaN never wins
-    }
-    return best;
-}
-
 // one lane per query (index[i] when an index list is given).  best_d2 / done carry the search from one grid to the next
 __global__ void __launch_bounds__(kCloudBlock) cloud_nn_distance_kernel(const float* __restrict__ q, long long nq,
                                                                         const long long* __restrict__ index, long long n_index,
@@ -157,33 +110,10 @@ __global__ void __launch_bounds__(kCloudBlock) cloud_nn_distance_kernel(const fl
         dist[i] = cap;
         return;
     }
-    const double clamp = kCellClamp;
-    const int cx = (int)fmin(fmax(cell_of(qx, g.ox, g.edge), -clamp), clamp), cy = (int)fmin(fmax(cell_of(qy, g.oy, g.edge), -clamp), clamp),
-              cz = (int)fmin(fmax(cell_of(qz, g.oz, g.edge), -clamp), clamp);
-    double best = best_d2[i];
-    bool found = false;
-    for (int r = 0; r <= rings; ++r) {
-        if (r >= 1) {                                      // every target of ring r or beyond is at least (r - 1) * edge away
-            const double lb = (double)(r - 1) * g.edge * kRingShrink;
-            if (best <= lb * lb || lb >= cap) {
-                found = true;
-                break;
-            }
-        }
-        if (r == rings) break;                             // this grid's rings are used up: the next grid goes on
-        const int x0 = cx - r > 0 ? cx - r : 0, x1 = cx + r < g.nx - 1 ? cx + r : g.nx - 1;
-        const int y0 = cy - r > 0 ? cy - r : 0, y1 = cy + r < g.ny - 1 ? cy + r : g.ny - 1;
-        for (int x = x0; x <= x1; ++x) {
-            for (int y = y0; y <= y1; ++y) {
-                if (x - cx == r || cx - x == r || y - cy == r || cy - y == r) {
-                    best = scan_cells(t, keys, nt, g, x, y, cz - r, cz + r, qx, qy, qz, best);
-                } else {                                   // inside the ring's square: its bottom and its lid
-                    best = scan_cells(t, keys, nt, g, x, y, cz - r, cz - r, qx, qy, qz, best);
-                    best = scan_cells(t, keys, nt, g, x, y, cz + r, cz + r, qx, qy, qz, best);
-                }
-            }
-        }
-    }
+    const int cx = clamped_cell(qx, g.ox, g.edge), cy = clamped_cell(qy, g.oy, g.edge), cz = clamped_cell(qz, g.oz, g.edge);
+    NearestDistance nearest{best_d2[i]};
+    const bool found = ring_walk(t, keys, nt, g, cx, cy, cz, qx, qy, qz, cap, rings, nearest);
+    const double best = nearest.d2;
     const double d = sqrt(best);
     best_d2[i] = best;
     done[i] = found ? 1 : 0;
@@ -202,22 +132,6 @@ __global__ void __launch_bounds__(kCloudBlock) cloud_in_mask_kernel(const float*
     if (vx > 0.0 && vx <= (double)sx && vy > 0.0 && vy <= (double)sy && vz > 0.0 && vz <= (double)sz)          // NaN: false
         in = mask[(((long long)vx - 1) * sy + ((long long)vy - 1)) * sz + ((long long)vz - 1)] != 0;
     out[i] = in;
-}
-
-static inline bool finite_all(double a, double b, double c, double d) {
-    return isfinite(a) && isfinite(b) && isfinite(c) && isfinite(d);
-}
-
-// ITERMVS_OK or the error of a grid description; n is the number of points of the launch
-static inline int check_grid(long long n, double ox, double oy, double oz, int nx, int ny, int nz, double edge) {
-    ITERMVS_RETURN_IF(n < 1 || n > 0x7fffff00LL, ITERMVS_ERR_DIMS);
-    ITERMVS_RETURN_IF(!finite_all(ox, oy, oz, edge) || !(edge > 0.0), ITERMVS_ERR_DIMS);
-    ITERMVS_RETURN_IF(nx < 1 || ny < 1 || nz < 1 || nx > kMaxCellDim || ny > kMaxCellDim || nz > kMaxCellDim, ITERMVS_ERR_DIMS);
-    return ITERMVS_OK;
-}
-
-static inline unsigned blocks_for(long long n) {
-    return (unsigned)((n + kCloudBlock - 1) / kCloudBlock);
 }
 
 }  // namespace itermvs

@@ -10,6 +10,7 @@ import ctypes as C
 import os
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1502,6 +1503,93 @@ def cloud_in_mask(xyz: Tensor, mask: Tensor, origin: Sequence[float], res: float
                                                 *[float(o) for o in origin], float(res), out.data_ptr(), _stream()),
               "itermvs_cloud_in_mask")
     return out
+
+
+def _transform(what: str, T) -> "C.Array":
+    m = np.asarray(T.cpu() if torch.is_tensor(T) else T, dtype=np.float64)
+    if m.shape != (4, 4):
+        raise RuntimeError(f"{what}: T must be a 4x4 matrix, got shape {m.shape}")
+    return (C.c_double * 16)(*[float(v) for v in m.reshape(-1)])
+
+
+def cloud_crop(xyz: Tensor, T, axis: int, axis_min: float, axis_max: float, polygon) -> Tensor:
+    """itermvs_cloud_crop: uint8 [n] = 1 where T * p lies in the prism (orthogonal ``axis`` 0/1/2, axis_min <= c <= axis_max, the
+    other two coordinates inside ``polygon``, a host [n_poly,3] fp64 array, by the even-odd rule of the header)."""
+    n = _cloud("cloud_crop", xyz, "xyz").shape[0]
+    poly = np.ascontiguousarray(np.asarray(polygon, dtype=np.float64))
+    if poly.ndim != 2 or poly.shape[1] != 3:
+        raise RuntimeError(f"cloud_crop: polygon must be [n_poly,3], got shape {poly.shape}")
+    out = torch.empty((n,), device=xyz.device, dtype=torch.uint8)
+    if n:
+        ws = torch.empty((max(2 * poly.shape[0], 1),), device=xyz.device, dtype=torch.float64)
+        check(_lib.load().itermvs_cloud_crop(xyz.data_ptr(), n, _transform("cloud_crop", T), int(axis), float(axis_min),
+                                             float(axis_max), poly.ctypes.data_as(C.POINTER(C.c_double)), poly.shape[0],
+                                             ws.data_ptr(), out.data_ptr(), _stream()), "itermvs_cloud_crop")
+    return out
+
+
+def cloud_voxel_heads(keys_sorted: Tensor) -> Tensor:
+    """itermvs_cloud_voxel_heads: int32 [n] = 1 at the first position of every run of equal keys (INT64_MAX keys: 0)"""
+    n = _cloud("cloud_voxel_heads", keys_sorted, "keys_sorted", torch.int64, ()).numel()
+    head = torch.empty((n,), device=keys_sorted.device, dtype=torch.int32)
+    if n:
+        check(_lib.load().itermvs_cloud_voxel_heads(keys_sorted.data_ptr(), n, head.data_ptr(), _stream()), "itermvs_cloud_voxel_heads")
+    return head
+
+
+def cloud_voxel_mean(xyz_sorted: Tensor, keys_sorted: Tensor, rank: Tensor, n_out: int) -> Tensor:
+    """itermvs_cloud_voxel_mean: float32 [n_out,3] = per run of equal keys the mean of its points (fp64 sum in sorted order, one
+    rounding), at the run's ``rank`` (int64 [n]: inclusive prefix sum of the heads, minus 1)"""
+    n = _cloud("cloud_voxel_mean", xyz_sorted, "xyz_sorted").shape[0]
+    for t, name in ((keys_sorted, "keys_sorted"), (rank, "rank")):
+        if _cloud("cloud_voxel_mean", t, name, torch.int64, ()).numel() != n:
+            raise RuntimeError(f"cloud_voxel_mean: {name} must have {n} elements, got {t.numel()}")
+    out = torch.zeros((max(int(n_out), 0), 3), device=xyz_sorted.device, dtype=torch.float32)
+    check(_lib.load().itermvs_cloud_voxel_mean(xyz_sorted.data_ptr(), keys_sorted.data_ptr(), rank.data_ptr(), n, int(n_out),
+                                               out.data_ptr(), _stream()), "itermvs_cloud_voxel_mean")
+    return out
+
+
+def cloud_nn_index(q: Tensor, T, to_sorted: Tensor, keys_sorted: Tensor, perm: Tensor, grid: CloudGrid, max_dist: float,
+                   rings: int) -> Tuple[Tensor, Tensor]:
+    """itermvs_cloud_nn_index: (idx int64 [nq], d2 float64 [nq]) = for every query T * q the nearest target with
+    d2 < max_dist^2 (exclusive), as ``perm[position]`` (ties: the lowest) or -1 / +Inf.  to_sorted float32 [nt,3], keys_sorted
+    and perm int64 [nt] in key order on ``grid``; nt may be 0."""
+    nq = _cloud("cloud_nn_index", q, "q").shape[0]
+    nt = _cloud("cloud_nn_index", to_sorted, "to_sorted").shape[0]
+    for t, name in ((keys_sorted, "keys_sorted"), (perm, "perm")):
+        if _cloud("cloud_nn_index", t, name, torch.int64, ()).numel() != nt:
+            raise RuntimeError(f"cloud_nn_index: {name} must have {nt} elements, got {t.numel()}")
+    idx = torch.empty((nq,), device=q.device, dtype=torch.int64)
+    d2 = torch.empty((nq,), device=q.device, dtype=torch.float64)
+    check(_lib.load().itermvs_cloud_nn_index(q.data_ptr(), nq, _transform("cloud_nn_index", T), _ptr(to_sorted) if nt else None,
+                                             _ptr(keys_sorted) if nt else None, _ptr(perm) if nt else None, nt, *grid.args(),
+                                             float(max_dist), int(rings), idx.data_ptr(), d2.data_ptr(), _stream()),
+          "itermvs_cloud_nn_index")
+    return idx, d2
+
+
+def cloud_umeyama_groups(n: int) -> int:
+    """itermvs_cloud_umeyama_groups: the number of workgroups (= rows of partials) the sums over n correspondences use"""
+    g = _lib.load().itermvs_cloud_umeyama_groups(int(n))
+    check(min(g, 0), "itermvs_cloud_umeyama_groups")
+    return g
+
+
+def cloud_umeyama_sums(q: Tensor, T, idx: Tensor, d2: Tensor, target: Tensor) -> Tensor:
+    """itermvs_cloud_umeyama_sums: float64 [18] on the device = {count, sum p, sum t, sum t p^T, sum |p|^2, sum d2} over the
+    correspondences idx[i] >= 0 with p = T * q_i and t = target[idx[i]] (the unsorted targets).  Nothing is read back."""
+    n = _cloud("cloud_umeyama_sums", q, "q").shape[0]
+    nt = _cloud("cloud_umeyama_sums", target, "target").shape[0]
+    for t, dt, name in ((idx, torch.int64, "idx"), (d2, torch.float64, "d2")):
+        if _cloud("cloud_umeyama_sums", t, name, dt, ()).numel() != n:
+            raise RuntimeError(f"cloud_umeyama_sums: {name} must have {n} elements, got {t.numel()}")
+    partials = torch.empty((max(cloud_umeyama_groups(n), 1) if n else 1, 18), device=q.device, dtype=torch.float64)
+    sums = torch.empty((18,), device=q.device, dtype=torch.float64)
+    check(_lib.load().itermvs_cloud_umeyama_sums(q.data_ptr(), n, _transform("cloud_umeyama_sums", T), idx.data_ptr(), d2.data_ptr(),
+                                                 _ptr(target) if nt else None, nt, partials.data_ptr(), sums.data_ptr(), _stream()),
+          "itermvs_cloud_umeyama_sums")
+    return sums
 
 
 CORRNET_WEIGHT_FLOATS = 14288
