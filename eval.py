@@ -13,7 +13,8 @@ repository's scope.  ``--filter`` runs the reference's filter / fusion stage (ev
 folder under ``--testpath`` that has a ``pair.txt``, ``cams_1/`` and ``images/``, the depth / confidence PFMs written above
 are fused into ``<outdir>/<scan>.ply`` by ``itermvs_amd.fusion.filter_depth`` (one HIP launch per reference view); the
 camera intrinsics are rescaled by ``--img_wh`` / original image size and the points coloured from the resized images like
-eval.py:231-232,251-252,295.
+eval.py:231-232,251-252,295.  ``--filter --fuse_source memory`` does both in one pass: each scan is fused from GPU memory when
+its last depth map is done (``itermvs_amd.scan_fuse``), ``--no_pfm`` then leaves only the PLYs on the disk.
 """
 from __future__ import annotations
 
@@ -77,8 +78,17 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--num_samples", type=int, default=8, help="synthetic dataset: number of reference views")
     p.add_argument("--filter", action="store_true", help="fuse the saved depth maps of every scan into a point cloud (eval.py:311-325)")
     p.add_argument("--fuse_points", default="host", choices=["host", "device"],
-                   help="--filter: where the surviving pixels become PLY vertices (eval.py:287-308): numpy on the host with one "
-                        "synchronisation per reference view (default), or itermvs_fuse_points on the GPU with one per group of views")
+                   help="--filter with --fuse_source files: where the surviving pixels become PLY vertices (eval.py:287-308): numpy "
+                        "on the host with one synchronisation per reference view (default), or itermvs_fuse_points on the GPU with "
+                        "one per group of views.  --fuse_source memory always assembles the vertex records on the GPU")
+    p.add_argument("--fuse_source", default="files", choices=["files", "memory"],
+                   help="--filter: what the fusion reads.  files (default): the PFMs and images, in a second pass after every depth "
+                        "map is written.  memory (needs --dataset folder): each scan is fused from GPU memory as soon as its last "
+                        "depth map is done -- no PFM is read back and no image is decoded twice (itermvs_amd.scan_fuse; ranks "
+                        "take whole scans; the PLY is byte for byte the one of --fuse_points device)")
+    p.add_argument("--no_pfm", action="store_true",
+                   help="--fuse_source memory only: do not write the depth / confidence PFMs, only the PLY (and the masks of "
+                        "--save_masks) reaches the disk")
     p.add_argument("--save_masks", action="store_true",
                    help="--filter: write <outdir>/<scan>/mask/<view>_photo.png, _geo.png, _final.png like the reference (eval.py:266-269)")
     return p
@@ -170,6 +180,36 @@ def check_feature_cache(args) -> int:
     if n > 0 and n < args.n_views:
         raise SystemExit(f"--feature_cache {n} is below --n_views {args.n_views}: a depth map's views must fit in the cache")
     return n
+
+
+def check_fuse_source(args) -> str:
+    """--fuse_source memory needs --dataset folder and --filter; --no_pfm needs --fuse_source memory"""
+    source = getattr(args, "fuse_source", "files")
+    if source == "memory":
+        missing = [flag for flag, ok in (("--dataset folder", args.dataset == "folder"), ("--filter", bool(args.filter))) if not ok]
+        if missing:
+            raise SystemExit("--fuse_source memory needs {} (scan folders with pair.txt, fused as their depth maps finish), got "
+                             "--dataset {}{}".format(" and ".join(missing), args.dataset, "" if args.filter else " without --filter"))
+    if getattr(args, "no_pfm", False) and source != "memory":
+        raise SystemExit("--no_pfm needs --fuse_source memory: --fuse_source files fuses the PFMs it would skip")
+    return source
+
+
+def fuse_memory(args) -> dict:
+    """--fuse_source memory: depth maps and point clouds in one pass (itermvs_amd.scan_fuse); scans are sharded over the
+    ranks whole, like ``fuse_scans`` shards them.  -> {scan: {ref_view: (geo, photo, final mask share)}} of this rank"""
+    from itermvs_amd.scan_fuse import fuse_scans_from_memory
+    check_fuse_source(args)
+    check_feature_cache(args)
+    rank, local_rank, world = shard.init_distributed()
+    torch.cuda.set_device(local_rank)
+    dev = torch.device("cuda", local_rank)
+    dataset = make_dataset(args)
+    model = load_model(args, dev)
+    scans = list(dict.fromkeys(m[0] for m in dataset.metas))
+    stats = fuse_scans_from_memory(args, dataset, [scans[i] for i in shard.shard_indices(len(scans), rank, world)], model, dev)
+    shard.barrier()
+    return stats
 
 
 def save_depth(args) -> int:
@@ -287,6 +327,9 @@ def fuse_scans(args) -> int:
 if __name__ == "__main__":
     a = build_parser().parse_args()
     print("argv:", sys.argv[1:])
-    save_depth(a)
-    if a.filter:
-        fuse_scans(a)
+    if check_fuse_source(a) == "memory":
+        fuse_memory(a)
+    else:
+        save_depth(a)
+        if a.filter:
+            fuse_scans(a)

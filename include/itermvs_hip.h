@@ -793,6 +793,22 @@ int itermvs_image_pyramid(const uint8_t* src, int32_t V, int32_t Hs, int32_t Ws,
                           float* level1, float* level2, float* level3, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * itermvs_resize_rgb8 -- Pillow's Image.resize((W, H), Image.BILINEAR) of 8-bit RGB images, bit for bit: the vertex colours
+ * of the fusion (eval.py:68-74,295 with PIL in cv2's place) from the uint8 upload of the input side.
+ *   src [V,Hs,Ws,3] uint8 -> out [V,H,W,3] uint8, out[v] == np.array(Image.fromarray(src[v]).resize((W, H), Image.BILINEAR)).
+ * Pillow's 8-bit resample is integer arithmetic on per-axis tables that the caller computes in doubles
+ * (itermvs_amd/resize.py) and passes as device memory:
+ *   xbounds [W,2] int32: first input column and tap count of every output column; xk [W,KX] int32: the taps with 22
+ *   fractional bits (KX >= every count);  ybounds [H,2], yk [H,KY]: the same for the rows.
+ *   pass = clip(((1 << 21) + sum(pixel[first + t] * k[t])) >> 22, 0, 255); horizontal first, its uint8 result feeds the
+ *   vertical pass.  An axis that keeps its size takes the identity table (count 1, tap 1 << 22).
+ * One launch; taps that a table places outside the image are clamped to it.
+ * ------------------------------------------------------------------------------------------ */
+int itermvs_resize_rgb8(const uint8_t* src, int32_t V, int32_t Hs, int32_t Ws, int32_t H, int32_t W, const int32_t* xbounds,
+                        const int32_t* xk, int32_t KX, const int32_t* ybounds, const int32_t* yk, int32_t KY, uint8_t* out,
+                        void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Training input side (csrc/train_input.hip).
  *
  * itermvs_image_pyramid_jitter -- datasets/dtu_yao.py:64-77 and datasets/blendedmvs.py:85-101 (read_img in train mode):

@@ -1833,6 +1833,37 @@ def image_pyramid(raw: Tensor, height: int, width: int, all_levels: bool = True,
     return out
 
 
+_RESIZE_TABLES: Dict[tuple, Tuple[Tensor, Tensor, Tensor, Tensor]] = {}
+
+
+def resize_rgb8(raw: Tensor, height: int, width: int) -> Tensor:
+    """itermvs_resize_rgb8: raw [V,Hs,Ws,3] uint8 RGB (device) -> uint8 [V,H,W,3], view for view the bytes of
+    ``np.array(Image.fromarray(raw[v]).resize((width, height), Image.BILINEAR))`` (the fusion's vertex colours,
+    fusion.read_scan_image(as_uint8=True)).  Pillow's coefficient tables come from ``resize.resize_tables`` (host doubles) and
+    stay on the device per (Hs, Ws, H, W); a resize to the same size returns a copy of the input bytes."""
+    if not raw.is_cuda or raw.dtype != torch.uint8 or raw.dim() != 4 or raw.shape[3] != 3:
+        raise RuntimeError("resize_rgb8: expected a CUDA uint8 tensor [V,Hs,Ws,3]")
+    height, width = int(height), int(width)
+    if height < 1 or width < 1:
+        raise RuntimeError(f"resize_rgb8: the output size must be positive, got {height} x {width}")
+    raw = raw.contiguous()
+    v, hs, ws, _ = raw.shape
+    if (hs, ws) == (height, width):
+        return raw.clone()
+    key = (hs, ws, height, width, raw.device)
+    tables = _RESIZE_TABLES.get(key)
+    if tables is None:
+        from .resize import resize_tables
+        tables = _RESIZE_TABLES[key] = tuple(torch.from_numpy(np.array(t)).to(raw.device)     # (the cached arrays are read-only)
+                                             for t in resize_tables(hs, ws, height, width))
+    xb, xk, yb, yk = tables
+    out = torch.empty((v, height, width, 3), device=raw.device, dtype=torch.uint8)
+    check(_lib.load().itermvs_resize_rgb8(raw.data_ptr(), v, hs, ws, height, width, xb.data_ptr(), xk.data_ptr(), xk.shape[1],
+                                          yb.data_ptr(), yk.data_ptr(), yk.shape[1], out.data_ptr(), _stream()),
+          "itermvs_resize_rgb8")
+    return out
+
+
 JITTER_BYTES = 16      # sizeof(itermvs_jitter): brightness f32, contrast f32, contrast_first i32, enabled i32
 
 

@@ -103,11 +103,14 @@ class ScanFolderDataset(torch.utils.data.Dataset):
                 "filename": scan + "/{}/" + "{:0>8}".format(view_ids[0]) + "{}"}
 
 
-def to_device(sample: dict, dev, all_levels: bool = False) -> Tuple[dict, dict, torch.Tensor, torch.Tensor]:
+def to_device(sample: dict, dev, all_levels: bool = False, keep: dict = None) -> Tuple[dict, dict, torch.Tensor, torch.Tensor]:
     """one ScanFolderDataset item -> (imgs, proj_matrices, depth_min, depth_max) on ``dev`` with a leading batch dimension
-    of 1, the images normalised / resized / pyramided by the HIP kernel on the current stream"""
+    of 1, the images normalised / resized / pyramided by the HIP kernel on the current stream.  ``keep``: a dict that
+    receives the device copy of the decoded bytes as ``keep['raw']`` ([V,Hs,Ws,3] uint8) for a caller that needs them again"""
     from . import ops
     raw = sample["raw"].to(dev, non_blocking=True)
+    if keep is not None:
+        keep["raw"] = raw
     w, h = sample["img_wh"]
     imgs = {k: v.unsqueeze(0) for k, v in ops.image_pyramid(raw, h, w, all_levels).items()}
     projs = {k: v.to(dev, non_blocking=True).unsqueeze(0) for k, v in sample["proj_matrices"].items()}
