@@ -619,233 +619,176 @@ extern "C" int itermvs_pvw_tail(const float* x, const float* w, const float* bia
     return itermvs_launch_status();
 }
 
+// The four fused entry points: check (corr_common.hpp), fill the kernel arguments, launch.  The direct and the slot form of
+// a branch differ only in the level descriptions the check hands back.
+constexpr int kCorrTile = 32;       // pixels per workgroup of the fused kernels
+
+static int corr_tiles(int W, int H) {
+    return ((W + kIterTW - 1) / kIterTW) * ((H + kCorrTile / kIterTW - 1) / (kCorrTile / kIterTW));
+}
+
 // Tile order of the iteration kernel (see xcd_tile_chunked): tiles per XCD band, 0 = one contiguous band per XCD.
 // A TUNING build takes ITERMVS_ITER_BAND_ROWS (tile rows per band; 0 = contiguous, -1 = plain interleaving) from the environment.
-static int iter_band_tiles(int tiles_x, int tiles, const itermvs_corr_iter_params* p) {
+static int iter_band_tiles(int W) {
     if (const char* e = itermvs_tuning_env("ITERMVS_ITER_BAND_ROWS")) {
         const int rows = atoi(e);
-        return rows < 0 ? 1 : rows * tiles_x;
+        return rows < 0 ? 1 : rows * ((W + kIterTW - 1) / kIterTW);
     }
-    (void)tiles; (void)p;
     return 0;
 }
 
-extern "C" int itermvs_corr_iter(const itermvs_corr_iter_params* p, void* stream) {
-    ITERMVS_RETURN_IF(!p, ITERMVS_ERR_NULL);
-    ITERMVS_RETURN_IF(p->B < 1 || p->H < 1 || p->W < 1, ITERMVS_ERR_DIMS);
-    ITERMVS_RETURN_IF(p->S < 1 || p->S > ITERMVS_MAX_SRC, ITERMVS_ERR_VIEWS);
-    ITERMVS_RETURN_IF(!p->ref_q || !p->proj || !p->view_w || !p->inv_depth_min || !p->inv_depth_max, ITERMVS_ERR_NULL);
-    ITERMVS_RETURN_IF(((uintptr_t)p->ref_q) % 16, ITERMVS_ERR_ALIGN);
-    for (int l = 0; l < 3; ++l) {
-        const int rc = itermvs_check_level(p->src[l], p->S);
-        if (rc) return rc;
-        ITERMVS_RETURN_IF(p->N[l] < 1 || p->N[l] > ITERMVS_MAX_HYP, ITERMVS_ERR_DIMS);
-        ITERMVS_RETURN_IF(!p->out[l], ITERMVS_ERR_NULL);
-        ITERMVS_RETURN_IF(!p->depth[l] && !p->norm_depth, ITERMVS_ERR_NULL);
-    }
-    IterArgs a;
-    int coff = 0;
-    for (int l = 0; l < 3; ++l) {
-        IterLevel& L = a.lv[l];
-        for (int v = 0; v < ITERMVS_MAX_SRC; ++v) L.src[v] = (const float*)p->src[l].view[v < p->S ? v : 0];
-        L.sb = p->src[l].sb; L.sy = p->src[l].sy; L.sx = p->src[l].sx;
-        L.depth = p->depth[l];
-        L.out = p->out[l];
-        for (int n = 0; n < ITERMVS_MAX_HYP; ++n) L.offs[n] = p->offsets[l][n];
-        L.C = p->src[l].C; L.H1 = p->src[l].H; L.W1 = p->src[l].W; L.N = p->N[l];
-        L.coff = coff;
-        coff += L.C;
-    }
-    a.ref_q = p->ref_q; a.proj = p->proj; a.view_w = p->view_w; a.nd = p->norm_depth; a.nd_sb = p->norm_depth_sb;
-    a.inv_min = p->inv_depth_min; a.inv_max = p->inv_depth_max;
-    a.B = p->B; a.S = p->S; a.H = p->H; a.W = p->W; a.CQ = coff;
-    a.band = 0;
-    if (p->view_w_sb == 0 && p->view_w_ss == 0 && p->view_w_sp == 0) {      // default: planar [B,S,H,W]
-        a.vw_sp = 1; a.vw_ss = (int64_t)p->H * p->W; a.vw_sb = a.vw_ss * p->S;
-    } else {
-        ITERMVS_RETURN_IF(p->view_w_ss < 1 || p->view_w_sp < 1 || p->view_w_sb < 0, ITERMVS_ERR_LAYOUT);
-        a.vw_sb = p->view_w_sb; a.vw_ss = p->view_w_ss; a.vw_sp = p->view_w_sp;
-    }
-    // One form: source views walked inside the lane.  (A views-across-waves form issued 14 % fewer vector instructions but
-    // missed the vector L1 31 % more often -- 33.4 vs 28.9 us, profiles/r02 -- and was removed; `impl` is reserved.)
-    ITERMVS_RETURN_IF(p->impl != 0, ITERMVS_ERR_DIMS);
-    const int dtype = p->src[0].dtype;
-    ITERMVS_RETURN_IF(p->src[1].dtype != dtype || p->src[2].dtype != dtype, ITERMVS_ERR_DTYPE);
-    itermvs_profile_begin(1, (hipStream_t)stream);
-    {
-        constexpr int TILE = 32;
-        const int tiles_x = (p->W + kIterTW - 1) / kIterTW;
-        const int tiles = tiles_x * ((p->H + TILE / kIterTW - 1) / (TILE / kIterTW));
-        a.band = iter_band_tiles(tiles_x, tiles, p);
-        const dim3 grid(a.band > 0 ? xcd_chunked_grid(tiles, a.band) : (unsigned)(((tiles + 7) / 8) * 8), 3, p->B);
-        switch (dtype) {
-            case ITERMVS_F16: hipLaunchKernelGGL((corr_iter_kernel<TILE, ITERMVS_F16>), grid, dim3(kThreads), 0, (hipStream_t)stream, a); break;
-            case ITERMVS_BF16: hipLaunchKernelGGL((corr_iter_kernel<TILE, ITERMVS_BF16>), grid, dim3(kThreads), 0, (hipStream_t)stream, a); break;
-#ifdef ITERMVS_ITER_TWO_PHASE
-            default: {
-                int nmax = 1;
-                for (int l = 0; l < 3; ++l) nmax = p->N[l] > nmax ? p->N[l] : nmax;
-                const size_t shm = (size_t)nmax * (ITERMVS_GROUPS * (TILE + 1) + TILE * 4 + TILE * 4 * 9) * 4;
-                hipLaunchKernelGGL((corr_iter2_kernel<TILE, ITERMVS_F32>), grid, dim3(kThreads), shm, (hipStream_t)stream, a, nmax);
-                break;
-            }
-#else
-            default: hipLaunchKernelGGL((corr_iter_kernel<TILE, ITERMVS_F32>), grid, dim3(kThreads), 0, (hipStream_t)stream, a); break;
-#endif
-        }
-    }
-    itermvs_profile_end(1, (hipStream_t)stream);
-    return itermvs_launch_status();
-}
-
-extern "C" int itermvs_corr_init(const itermvs_corr_init_params* p, void* stream) {
-    ITERMVS_RETURN_IF(!p, ITERMVS_ERR_NULL);
-    ITERMVS_RETURN_IF(p->B < 1 || p->H < 1 || p->W < 1 || p->N < 2, ITERMVS_ERR_DIMS);
-    ITERMVS_RETURN_IF(p->S < 1 || p->S > ITERMVS_MAX_SRC, ITERMVS_ERR_VIEWS);
-    ITERMVS_RETURN_IF(!p->ref.data || !p->proj || !p->inv_depth_min || !p->inv_depth_max || !p->out, ITERMVS_ERR_NULL);
-    const int rc = itermvs_check_level(p->src, p->S);
-    if (rc) return rc;
-    ITERMVS_RETURN_IF(p->ref.C != p->src.C || p->ref.H != p->H || p->ref.W != p->W, ITERMVS_ERR_DIMS);
-    InitArgs a;
-    for (int v = 0; v < ITERMVS_MAX_SRC; ++v) a.src[v] = (const float*)p->src.view[v < p->S ? v : 0];
-    a.sb = p->src.sb; a.sy = p->src.sy; a.sx = p->src.sx;
-    a.ref = p->ref; a.proj = p->proj; a.depth = p->depth;
-    a.inv_min = p->inv_depth_min; a.inv_max = p->inv_depth_max; a.out = p->out;
-    a.B = p->B; a.S = p->S; a.H = p->H; a.W = p->W; a.N = p->N;
-    a.C = p->src.C; a.H1 = p->src.H; a.W1 = p->src.W; a.NB = kInitNB;
-    ITERMVS_RETURN_IF(p->out_layout != 0 && p->out_layout != 1, ITERMVS_ERR_LAYOUT);
-    ITERMVS_RETURN_IF(p->out_layout == 1 && ((uintptr_t)p->out) % 16, ITERMVS_ERR_ALIGN);
-    a.out_cl = p->out_layout;
-    constexpr int TILE = 32;
-    const int nblocks = (p->N + kInitNB - 1) / kInitNB;
-    itermvs_profile_begin(2, (hipStream_t)stream);
-    ITERMVS_RETURN_IF(p->ref.dtype != p->src.dtype, ITERMVS_ERR_DTYPE);
-#ifdef ITERMVS_INIT_SWEEP_BUILD
-    // the plane sweep through LDS (A/B builds only, see above): 48 fp32 channels; explicit per-pixel hypotheses are accepted (boxes
-    // that do not fit take the memory taps), coordinates must fit the packed 16-bit box reduction
-    static const bool sweep_on = [] { const char* e = getenv("ITERMVS_INIT_SWEEP"); return !e || e[0] != '0'; }();
-    if (sweep_on && a.C == 48 && p->src.dtype == ITERMVS_F32 && p->src.H < 65535 && p->src.W < 65535) {
-        const int tiles_x = (p->W + 7) / 8, tiles_y = (p->H + 7) / 8;
-        // planes per wave: four waves of a workgroup take consecutive plane blocks of one (tile, view); as many workgroups per
-        // (tile, view) as it takes to give every SIMD about two waves
-        const int64_t tv = (int64_t)tiles_x * tiles_y * p->S * p->B;
-        // (two waves per SIMD are resident: LDS.  More waves than that run in rounds -- give a wave twice the planes instead,
-        //  as long as every SIMD still gets a wave)
-        int ppw = 1;
-        while (ppw < 8 && tv * ((p->N + 4 * ppw - 1) / (4 * ppw)) * 4 > 2 * 4 * (int64_t)itermvs_num_cus() &&
-               tv * ((p->N + 8 * ppw - 1) / (8 * ppw)) * 4 >= 4 * (int64_t)itermvs_num_cus()) ppw *= 2;
-        const int groups = (p->N + 4 * ppw - 1) / (4 * ppw);
-        const dim3 grid(((tiles_x * tiles_y + 7) / 8) * 8, p->S * groups, p->B);
-        hipLaunchKernelGGL(corr_init_sweep_kernel, grid, dim3(256), 4 * kSweepWaveLds, (hipStream_t)stream, a, ppw, tiles_x, tiles_y);
-        itermvs_profile_end(2, (hipStream_t)stream);
-        return itermvs_launch_status();
-    }
-#endif
-    const int tiles = ((p->W + kIterTW - 1) / kIterTW) * ((p->H + TILE / kIterTW - 1) / (TILE / kIterTW));
-    const dim3 grid(((tiles + 7) / 8) * 8, p->S * nblocks, p->B);
-    switch (p->src.dtype) {
-        case ITERMVS_F16: hipLaunchKernelGGL((corr_init_kernel<TILE, ITERMVS_F16>), grid, dim3(kThreads), 0, (hipStream_t)stream, a); break;
-        case ITERMVS_BF16: hipLaunchKernelGGL((corr_init_kernel<TILE, ITERMVS_BF16>), grid, dim3(kThreads), 0, (hipStream_t)stream, a); break;
-        default: hipLaunchKernelGGL((corr_init_kernel<TILE, ITERMVS_F32>), grid, dim3(kThreads), 0, (hipStream_t)stream, a); break;
-    }
-    itermvs_profile_end(2, (hipStream_t)stream);
-    return itermvs_launch_status();
-}
-
-// The slot forms: the same parameter blocks with p->src replaced by slab + slot table (include/itermvs_hip.h).
-extern "C" int itermvs_corr_iter_slots(const itermvs_corr_iter_params* p, const itermvs_level_slots* src, void* stream) {
-    ITERMVS_RETURN_IF(!p || !src, ITERMVS_ERR_NULL);
-    ITERMVS_RETURN_IF(p->B < 1 || p->H < 1 || p->W < 1, ITERMVS_ERR_DIMS);
-    ITERMVS_RETURN_IF(p->S < 1 || p->S > ITERMVS_MAX_SRC, ITERMVS_ERR_VIEWS);
-    ITERMVS_RETURN_IF(!p->ref_q || !p->proj || !p->view_w || !p->inv_depth_min || !p->inv_depth_max, ITERMVS_ERR_NULL);
-    ITERMVS_RETURN_IF(((uintptr_t)p->ref_q) % 16, ITERMVS_ERR_ALIGN);
-    for (int l = 0; l < 3; ++l) {
-        const int rc = itermvs_check_slots(src[l]);
-        if (rc) return rc;
-        ITERMVS_RETURN_IF(p->N[l] < 1 || p->N[l] > ITERMVS_MAX_HYP, ITERMVS_ERR_DIMS);
-        ITERMVS_RETURN_IF(!p->out[l], ITERMVS_ERR_NULL);
-        ITERMVS_RETURN_IF(!p->depth[l] && !p->norm_depth, ITERMVS_ERR_NULL);
-    }
-    ITERMVS_RETURN_IF(p->impl != 0, ITERMVS_ERR_DIMS);
-    const int dtype = src[0].dtype;
-    ITERMVS_RETURN_IF(src[1].dtype != dtype || src[2].dtype != dtype, ITERMVS_ERR_DTYPE);
-    IterSlotArgs sa;
+static void fill_iter_args(IterSlotArgs& sa, const itermvs_corr_iter_params& p, const itermvs_level_desc (&lv)[3]) {
     IterArgs& a = sa.a;
     int coff = 0;
     for (int l = 0; l < 3; ++l) {
         IterLevel& L = a.lv[l];
-        for (int v = 0; v < ITERMVS_MAX_SRC; ++v) L.src[v] = (const float*)src[l].slab;
-        L.sb = src[l].slot_stride; L.sy = src[l].sy; L.sx = src[l].sx;
-        L.depth = p->depth[l];
-        L.out = p->out[l];
-        for (int n = 0; n < ITERMVS_MAX_HYP; ++n) L.offs[n] = p->offsets[l][n];
-        L.C = src[l].C; L.H1 = src[l].H; L.W1 = src[l].W; L.N = p->N[l];
+        for (int v = 0; v < ITERMVS_MAX_SRC; ++v) L.src[v] = (const float*)lv[l].base[v];
+        L.sb = lv[l].stride; L.sy = lv[l].sy; L.sx = lv[l].sx;
+        L.depth = p.depth[l];
+        L.out = p.out[l];
+        for (int n = 0; n < ITERMVS_MAX_HYP; ++n) L.offs[n] = p.offsets[l][n];
+        L.C = lv[l].C; L.H1 = lv[l].H; L.W1 = lv[l].W; L.N = p.N[l];
         L.coff = coff;
         coff += L.C;
-        sa.slot[l] = src[l].slot;
-        sa.n_slots[l] = src[l].n_slots;
+        sa.slot[l] = lv[l].slot; sa.n_slots[l] = lv[l].n_slots;
     }
-    a.ref_q = p->ref_q; a.proj = p->proj; a.view_w = p->view_w; a.nd = p->norm_depth; a.nd_sb = p->norm_depth_sb;
-    a.inv_min = p->inv_depth_min; a.inv_max = p->inv_depth_max;
-    a.B = p->B; a.S = p->S; a.H = p->H; a.W = p->W; a.CQ = coff;
-    a.band = 0;
-    if (p->view_w_sb == 0 && p->view_w_ss == 0 && p->view_w_sp == 0) {
-        a.vw_sp = 1; a.vw_ss = (int64_t)p->H * p->W; a.vw_sb = a.vw_ss * p->S;
+    a.ref_q = p.ref_q; a.proj = p.proj; a.view_w = p.view_w; a.nd = p.norm_depth; a.nd_sb = p.norm_depth_sb;
+    a.inv_min = p.inv_depth_min; a.inv_max = p.inv_depth_max;
+    a.B = p.B; a.S = p.S; a.H = p.H; a.W = p.W; a.CQ = coff;
+    if (p.view_w_sb == 0 && p.view_w_ss == 0 && p.view_w_sp == 0) {      // default: planar [B,S,H,W]
+        a.vw_sp = 1; a.vw_ss = (int64_t)p.H * p.W; a.vw_sb = a.vw_ss * p.S;
     } else {
-        ITERMVS_RETURN_IF(p->view_w_ss < 1 || p->view_w_sp < 1 || p->view_w_sb < 0, ITERMVS_ERR_LAYOUT);
-        a.vw_sb = p->view_w_sb; a.vw_ss = p->view_w_ss; a.vw_sp = p->view_w_sp;
+        a.vw_sb = p.view_w_sb; a.vw_ss = p.view_w_ss; a.vw_sp = p.view_w_sp;
     }
-    itermvs_profile_begin(1, (hipStream_t)stream);
-    {
-        constexpr int TILE = 32;
-        const int tiles_x = (p->W + kIterTW - 1) / kIterTW;
-        const int tiles = tiles_x * ((p->H + TILE / kIterTW - 1) / (TILE / kIterTW));
-        a.band = iter_band_tiles(tiles_x, tiles, p);
-        const dim3 grid(a.band > 0 ? xcd_chunked_grid(tiles, a.band) : (unsigned)(((tiles + 7) / 8) * 8), 3, p->B);
-        switch (dtype) {
-            case ITERMVS_F16: hipLaunchKernelGGL((corr_iter_slots_kernel<TILE, ITERMVS_F16>), grid, dim3(kThreads), 0, (hipStream_t)stream, sa); break;
-            case ITERMVS_BF16: hipLaunchKernelGGL((corr_iter_slots_kernel<TILE, ITERMVS_BF16>), grid, dim3(kThreads), 0, (hipStream_t)stream, sa); break;
-            default: hipLaunchKernelGGL((corr_iter_slots_kernel<TILE, ITERMVS_F32>), grid, dim3(kThreads), 0, (hipStream_t)stream, sa); break;
-        }
+    a.band = iter_band_tiles(p.W);
+}
+
+// the kernel of each form for a storage type
+template <class Args>
+using CorrKernel = void (*)(Args);
+#define ITERMVS_BY_DTYPE(kernel, dtype)                                  \
+    switch (dtype) {                                                     \
+        case ITERMVS_F16: return kernel<kCorrTile, ITERMVS_F16>;         \
+        case ITERMVS_BF16: return kernel<kCorrTile, ITERMVS_BF16>;       \
+        default: return kernel<kCorrTile, ITERMVS_F32>;                  \
     }
-    itermvs_profile_end(1, (hipStream_t)stream);
+static CorrKernel<IterArgs> iter_kernel(int dtype) { ITERMVS_BY_DTYPE(corr_iter_kernel, dtype) }
+static CorrKernel<InitArgs> init_kernel(int dtype) { ITERMVS_BY_DTYPE(corr_init_kernel, dtype) }
+static CorrKernel<IterSlotArgs> iter_slots_kernel(int dtype) { ITERMVS_BY_DTYPE(corr_iter_slots_kernel, dtype) }
+static CorrKernel<InitSlotArgs> init_slots_kernel(int dtype) { ITERMVS_BY_DTYPE(corr_init_slots_kernel, dtype) }
+
+static int launch_iter(const IterSlotArgs& sa, int dtype, hipStream_t stream) {
+    const IterArgs& a = sa.a;
+    const int tiles = corr_tiles(a.W, a.H);
+    const dim3 grid(a.band > 0 ? xcd_chunked_grid(tiles, a.band) : (unsigned)(((tiles + 7) / 8) * 8), 3, a.B);
+    itermvs_profile_begin(1, stream);
+    if (sa.slot[0]) {
+        hipLaunchKernelGGL(iter_slots_kernel(dtype), grid, dim3(kThreads), 0, stream, sa);
+#ifdef ITERMVS_ITER_TWO_PHASE
+    } else if (dtype == ITERMVS_F32) {
+        int nmax = 1;
+        for (int l = 0; l < 3; ++l) nmax = a.lv[l].N > nmax ? a.lv[l].N : nmax;
+        const size_t shm = (size_t)nmax * (ITERMVS_GROUPS * (kCorrTile + 1) + kCorrTile * 4 + kCorrTile * 4 * 9) * 4;
+        hipLaunchKernelGGL((corr_iter2_kernel<kCorrTile, ITERMVS_F32>), grid, dim3(kThreads), shm, stream, a, nmax);
+#endif
+    } else {
+        hipLaunchKernelGGL(iter_kernel(dtype), grid, dim3(kThreads), 0, stream, a);
+    }
+    itermvs_profile_end(1, stream);
     return itermvs_launch_status();
 }
 
-extern "C" int itermvs_corr_init_slots(const itermvs_corr_init_params* p, const itermvs_level_slots* src, void* stream) {
+template <class Src>
+static int corr_iter_entry(const itermvs_corr_iter_params* p, const Src* src, void* stream) {
     ITERMVS_RETURN_IF(!p || !src, ITERMVS_ERR_NULL);
-    ITERMVS_RETURN_IF(p->B < 1 || p->H < 1 || p->W < 1 || p->N < 2, ITERMVS_ERR_DIMS);
-    ITERMVS_RETURN_IF(p->S < 1 || p->S > ITERMVS_MAX_SRC, ITERMVS_ERR_VIEWS);
-    ITERMVS_RETURN_IF(!p->ref.data || !p->proj || !p->inv_depth_min || !p->inv_depth_max || !p->out, ITERMVS_ERR_NULL);
-    const int rc = itermvs_check_slots(*src);
+    itermvs_level_desc lv[3];
+    const int rc = itermvs_check_iter_params(*p, src, true, lv);
     if (rc) return rc;
-    ITERMVS_RETURN_IF(p->ref.C != src->C || p->ref.H != p->H || p->ref.W != p->W, ITERMVS_ERR_DIMS);
-    ITERMVS_RETURN_IF(p->ref.dtype != src->dtype, ITERMVS_ERR_DTYPE);
-    ITERMVS_RETURN_IF(p->out_layout != 0 && p->out_layout != 1, ITERMVS_ERR_LAYOUT);
-    ITERMVS_RETURN_IF(p->out_layout == 1 && ((uintptr_t)p->out) % 16, ITERMVS_ERR_ALIGN);
-    InitSlotArgs sa;
+    IterSlotArgs sa;
+    fill_iter_args(sa, *p, lv);
+    return launch_iter(sa, lv[0].dtype, (hipStream_t)stream);
+}
+
+static void fill_init_args(InitSlotArgs& sa, const itermvs_corr_init_params& p, const itermvs_level_desc& d) {
     InitArgs& a = sa.a;
-    for (int v = 0; v < ITERMVS_MAX_SRC; ++v) a.src[v] = (const float*)src->slab;
-    a.sb = src->slot_stride; a.sy = src->sy; a.sx = src->sx;
-    a.ref = p->ref; a.proj = p->proj; a.depth = p->depth;
-    a.inv_min = p->inv_depth_min; a.inv_max = p->inv_depth_max; a.out = p->out;
-    a.B = p->B; a.S = p->S; a.H = p->H; a.W = p->W; a.N = p->N;
-    a.C = src->C; a.H1 = src->H; a.W1 = src->W; a.NB = kInitNB;
-    a.out_cl = p->out_layout;
-    sa.slot = src->slot;
-    sa.n_slots = src->n_slots;
-    constexpr int TILE = 32;
-    const int nblocks = (p->N + kInitNB - 1) / kInitNB;
-    const int tiles = ((p->W + kIterTW - 1) / kIterTW) * ((p->H + TILE / kIterTW - 1) / (TILE / kIterTW));
-    const dim3 grid(((tiles + 7) / 8) * 8, p->S * nblocks, p->B);
-    itermvs_profile_begin(2, (hipStream_t)stream);
-    switch (src->dtype) {
-        case ITERMVS_F16: hipLaunchKernelGGL((corr_init_slots_kernel<TILE, ITERMVS_F16>), grid, dim3(kThreads), 0, (hipStream_t)stream, sa); break;
-        case ITERMVS_BF16: hipLaunchKernelGGL((corr_init_slots_kernel<TILE, ITERMVS_BF16>), grid, dim3(kThreads), 0, (hipStream_t)stream, sa); break;
-        default: hipLaunchKernelGGL((corr_init_slots_kernel<TILE, ITERMVS_F32>), grid, dim3(kThreads), 0, (hipStream_t)stream, sa); break;
+    for (int v = 0; v < ITERMVS_MAX_SRC; ++v) a.src[v] = (const float*)d.base[v];
+    a.sb = d.stride; a.sy = d.sy; a.sx = d.sx;
+    a.ref = p.ref; a.proj = p.proj; a.depth = p.depth;
+    a.inv_min = p.inv_depth_min; a.inv_max = p.inv_depth_max; a.out = p.out;
+    a.B = p.B; a.S = p.S; a.H = p.H; a.W = p.W; a.N = p.N;
+    a.C = d.C; a.H1 = d.H; a.W1 = d.W; a.NB = kInitNB;
+    a.out_cl = p.out_layout;
+    sa.slot = d.slot; sa.n_slots = d.n_slots;
+}
+
+#ifdef ITERMVS_INIT_SWEEP_BUILD
+// the plane sweep through LDS (A/B builds only, see above): 48 fp32 channels of the direct form; explicit per-pixel hypotheses
+// are accepted (boxes that do not fit take the memory taps), coordinates must fit the packed 16-bit box reduction
+static bool init_sweep_serves(const InitSlotArgs& sa, int dtype) {
+    static const bool sweep_on = [] { const char* e = getenv("ITERMVS_INIT_SWEEP"); return !e || e[0] != '0'; }();
+    return sweep_on && !sa.slot && sa.a.C == 48 && dtype == ITERMVS_F32 && sa.a.H1 < 65535 && sa.a.W1 < 65535;
+}
+
+static void launch_init_sweep(const InitArgs& a, hipStream_t stream) {
+    const int tiles_x = (a.W + 7) / 8, tiles_y = (a.H + 7) / 8;
+    // planes per wave: four waves of a workgroup take consecutive plane blocks of one (tile, view); as many workgroups per
+    // (tile, view) as it takes to give every SIMD about two waves
+    const int64_t tv = (int64_t)tiles_x * tiles_y * a.S * a.B;
+    // (two waves per SIMD are resident: LDS.  More waves than that run in rounds -- give a wave twice the planes instead,
+    //  as long as every SIMD still gets a wave)
+    int ppw = 1;
+    while (ppw < 8 && tv * ((a.N + 4 * ppw - 1) / (4 * ppw)) * 4 > 2 * 4 * (int64_t)itermvs_num_cus() &&
+           tv * ((a.N + 8 * ppw - 1) / (8 * ppw)) * 4 >= 4 * (int64_t)itermvs_num_cus()) ppw *= 2;
+    const int groups = (a.N + 4 * ppw - 1) / (4 * ppw);
+    const dim3 grid(((tiles_x * tiles_y + 7) / 8) * 8, a.S * groups, a.B);
+    hipLaunchKernelGGL(corr_init_sweep_kernel, grid, dim3(256), 4 * kSweepWaveLds, stream, a, ppw, tiles_x, tiles_y);
+}
+#endif
+
+static int launch_init(const InitSlotArgs& sa, int dtype, hipStream_t stream) {
+    const InitArgs& a = sa.a;
+    const int nblocks = (a.N + kInitNB - 1) / kInitNB;
+    const dim3 grid(((corr_tiles(a.W, a.H) + 7) / 8) * 8, a.S * nblocks, a.B);
+    itermvs_profile_begin(2, stream);
+    if (sa.slot) {
+        hipLaunchKernelGGL(init_slots_kernel(dtype), grid, dim3(kThreads), 0, stream, sa);
+#ifdef ITERMVS_INIT_SWEEP_BUILD
+    } else if (init_sweep_serves(sa, dtype)) {
+        launch_init_sweep(a, stream);
+#endif
+    } else {
+        hipLaunchKernelGGL(init_kernel(dtype), grid, dim3(kThreads), 0, stream, a);
     }
-    itermvs_profile_end(2, (hipStream_t)stream);
+    itermvs_profile_end(2, stream);
     return itermvs_launch_status();
+}
+
+template <class Src>
+static int corr_init_entry(const itermvs_corr_init_params* p, const Src* src, void* stream) {
+    ITERMVS_RETURN_IF(!p || !src, ITERMVS_ERR_NULL);
+    itermvs_level_desc d;
+    const int rc = itermvs_check_init_params(*p, *src, true, d);
+    if (rc) return rc;
+    InitSlotArgs sa;
+    fill_init_args(sa, *p, d);
+    return launch_init(sa, d.dtype, (hipStream_t)stream);
+}
+
+extern "C" int itermvs_corr_iter(const itermvs_corr_iter_params* p, void* stream) {
+    return corr_iter_entry(p, p ? p->src : nullptr, stream);
+}
+
+extern "C" int itermvs_corr_init(const itermvs_corr_init_params* p, void* stream) {
+    return corr_init_entry(p, p ? &p->src : nullptr, stream);
+}
+
+// The slot forms: the same parameter blocks with p->src replaced by slab + slot table (include/itermvs_hip.h).
+extern "C" int itermvs_corr_iter_slots(const itermvs_corr_iter_params* p, const itermvs_level_slots* src, void* stream) {
+    return corr_iter_entry(p, src, stream);
+}
+
+extern "C" int itermvs_corr_init_slots(const itermvs_corr_init_params* p, const itermvs_level_slots* src, void* stream) {
+    return corr_init_entry(p, src, stream);
 }
 
 extern "C" int itermvs_view_aggregate(const float* corr, const float* w, int32_t S, int32_t B, int32_t N, int32_t P,

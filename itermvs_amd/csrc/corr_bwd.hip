@@ -452,39 +452,35 @@ static int launch_gather(const BwdArgs& a, int dtype, dim3 grid, hipStream_t str
     return itermvs_launch_status();
 }
 
-static int fill_level(BwdLevel& L, const itermvs_level_src& s, float* const* gsrc, int S) {
-    const int rc = itermvs_check_level(s, S);
-    if (rc) return rc;
+static int fill_level(BwdLevel& L, const itermvs_level_desc& d, float* const* gsrc, int S) {
     for (int v = 0; v < ITERMVS_MAX_SRC; ++v) {
-        L.src[v] = (const float*)s.view[v < S ? v : 0];
+        L.src[v] = (const float*)d.base[v];
         L.gsrc[v] = gsrc[v < S ? v : 0];
         ITERMVS_RETURN_IF(!L.gsrc[v], ITERMVS_ERR_NULL);
     }
-    L.sb = s.sb; L.sy = s.sy; L.sx = s.sx;
-    L.C = s.C; L.H1 = s.H; L.W1 = s.W;
+    L.sb = d.stride; L.sy = d.sy; L.sx = d.sx;
+    L.C = d.C; L.H1 = d.H; L.W1 = d.W;
     return ITERMVS_OK;
 }
 
 extern "C" int itermvs_corr_iter_backward(const itermvs_corr_iter_params* p, const float* const grad_out[3],
                                           float* const* const grad_src[3], float* grad_ref_q, void* stream) {
     ITERMVS_RETURN_IF(!p || !grad_out || !grad_src || !grad_ref_q, ITERMVS_ERR_NULL);
-    ITERMVS_RETURN_IF(p->B < 1 || p->H < 1 || p->W < 1, ITERMVS_ERR_DIMS);
-    ITERMVS_RETURN_IF(p->S < 1 || p->S > ITERMVS_MAX_SRC, ITERMVS_ERR_VIEWS);
-    ITERMVS_RETURN_IF(!p->ref_q || !p->proj || !p->view_w || !p->inv_depth_min || !p->inv_depth_max, ITERMVS_ERR_NULL);
+    for (int l = 0; l < 3; ++l) ITERMVS_RETURN_IF(!grad_out[l] || !grad_src[l], ITERMVS_ERR_NULL);
     // the gradient kernels read the view weights in the contiguous [B,S,H,W] form only
     ITERMVS_RETURN_IF((p->view_w_sb || p->view_w_ss || p->view_w_sp) &&
                       !(p->view_w_sp == 1 && p->view_w_ss == (int64_t)p->H * p->W && p->view_w_sb == (int64_t)p->S * p->H * p->W),
                       ITERMVS_ERR_LAYOUT);
+    itermvs_level_desc lv[3];
+    const int rc = itermvs_check_iter_params(*p, p->src, false, lv);
+    if (rc) return rc;
     BwdArgs a;
-    const int cq = p->src[0].C + p->src[1].C + p->src[2].C;
+    const int cq = lv[0].C + lv[1].C + lv[2].C;
     int coff = 0;
     for (int l = 0; l < 3; ++l) {
         BwdLevel& L = a.lv[l];
-        ITERMVS_RETURN_IF(!grad_out[l] || !grad_src[l], ITERMVS_ERR_NULL);
-        const int rc = fill_level(L, p->src[l], grad_src[l], p->S);
-        if (rc) return rc;
-        ITERMVS_RETURN_IF(p->N[l] < 1 || p->N[l] > ITERMVS_MAX_HYP, ITERMVS_ERR_DIMS);
-        ITERMVS_RETURN_IF(!p->depth[l] && !p->norm_depth, ITERMVS_ERR_NULL);
+        const int rc2 = fill_level(L, lv[l], grad_src[l], p->S);
+        if (rc2) return rc2;
         L.depth = p->depth[l];
         L.gout = grad_out[l];
         L.ref = p->ref_q + coff;
@@ -499,23 +495,24 @@ extern "C" int itermvs_corr_iter_backward(const itermvs_corr_iter_params* p, con
     a.inv_min = p->inv_depth_min; a.inv_max = p->inv_depth_max;
     a.B = p->B; a.S = p->S; a.H = p->H; a.W = p->W; a.init = 0; a.vch = 4; a.hyp_chunks = 1; a.scatter = 1;
     const int P = p->H * p->W;
-    ITERMVS_RETURN_IF(p->src[1].dtype != p->src[0].dtype || p->src[2].dtype != p->src[0].dtype, ITERMVS_ERR_DTYPE);
-    return launch_bwd(a, p->src[0].dtype, dim3((((P + kBwdTile - 1) / kBwdTile + 7) / 8) * 8, 3, p->B), (hipStream_t)stream);
+    return launch_bwd(a, lv[0].dtype, dim3((((P + kBwdTile - 1) / kBwdTile + 7) / 8) * 8, 3, p->B), (hipStream_t)stream);
 }
 
 extern "C" int itermvs_corr_init_backward(const itermvs_corr_init_params* p, const float* grad_out, float* const* grad_src,
                                           float* grad_ref, void* stream) {
     ITERMVS_RETURN_IF(p && p->out_layout != 0, ITERMVS_ERR_LAYOUT);      // grad_out is [B,S,N,8,H,W]
     ITERMVS_RETURN_IF(!p || !grad_out || !grad_src || !grad_ref, ITERMVS_ERR_NULL);
-    ITERMVS_RETURN_IF(p->B < 1 || p->H < 1 || p->W < 1 || p->N < 2 || p->N > 32, ITERMVS_ERR_DIMS);
-    ITERMVS_RETURN_IF(p->S < 1 || p->S > ITERMVS_MAX_SRC, ITERMVS_ERR_VIEWS);
-    ITERMVS_RETURN_IF(!p->ref.data || !p->proj || !p->inv_depth_min || !p->inv_depth_max, ITERMVS_ERR_NULL);
-    ITERMVS_RETURN_IF(p->ref.sc != 1 || p->ref.C != p->src.C || p->ref.H != p->H || p->ref.W != p->W, ITERMVS_ERR_LAYOUT);
+    ITERMVS_RETURN_IF(p->N > 32, ITERMVS_ERR_DIMS);
+    itermvs_level_desc d;
+    const int rc = itermvs_check_init_params(*p, p->src, false, d);
+    if (rc) return rc;
+    // the reference map is read, and grad_ref written, with the kernels' channels-last addressing
+    ITERMVS_RETURN_IF(p->ref.sc != 1, ITERMVS_ERR_LAYOUT);
     ITERMVS_RETURN_IF((p->ref.sx % 4) || (p->ref.sy % 4) || (p->ref.sb % 4) || ((uintptr_t)p->ref.data % 16), ITERMVS_ERR_ALIGN);
     BwdArgs a;
     BwdLevel& L = a.lv[0];
-    const int rc = fill_level(L, p->src, grad_src, p->S);
-    if (rc) return rc;
+    const int rc1 = fill_level(L, d, grad_src, p->S);
+    if (rc1) return rc1;
     L.depth = p->depth;
     L.gout = grad_out;
     L.ref = (const float*)p->ref.data;
@@ -533,9 +530,8 @@ extern "C" int itermvs_corr_init_backward(const itermvs_corr_init_params* p, con
     // line comes near the source image or whose homography is singular: those are scattered here (mode 2, plane_inverse)
     a.scatter = p->depth ? 1 : 2;
     const int P = p->H * p->W;
-    ITERMVS_RETURN_IF(p->ref.dtype != p->src.dtype, ITERMVS_ERR_DTYPE);
-    const int rc2 = launch_bwd(a, p->src.dtype, dim3((((P + kBwdTile - 1) / kBwdTile + 7) / 8) * 8, p->S * a.hyp_chunks, p->B), (hipStream_t)stream);
+    const int rc2 = launch_bwd(a, d.dtype, dim3((((P + kBwdTile - 1) / kBwdTile + 7) / 8) * 8, p->S * a.hyp_chunks, p->B), (hipStream_t)stream);
     if (rc2 || a.scatter == 1) return rc2;
-    const int P1 = p->src.H * p->src.W;
-    return launch_gather(a, p->src.dtype, dim3((((P1 + 15) / 16 + 7) / 8) * 8, p->S, p->B), (hipStream_t)stream);
+    const int P1 = d.H * d.W;
+    return launch_gather(a, d.dtype, dim3((((P1 + 15) / 16 + 7) / 8) * 8, p->S, p->B), (hipStream_t)stream);
 }

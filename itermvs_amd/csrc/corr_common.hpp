@@ -449,17 +449,40 @@ struct IterArgs {
 
 }  // namespace itermvs
 
-// argument checks shared by the forward and backward entry points
-static inline int itermvs_check_level(const itermvs_level_src& s, int S) {
-    ITERMVS_RETURN_IF(s.C != 16 && s.C != 32 && s.C != 48, ITERMVS_ERR_CHANNELS);
-    ITERMVS_RETURN_IF(s.H < 1 || s.W < 1, ITERMVS_ERR_DIMS);
-    ITERMVS_RETURN_IF(s.sc != 1, ITERMVS_ERR_LAYOUT);
-    ITERMVS_RETURN_IF(s.dtype < ITERMVS_F32 || s.dtype > ITERMVS_BF16, ITERMVS_ERR_DTYPE);
-    ITERMVS_RETURN_IF((s.sx % 4) || (s.sy % 4) || (s.sb % 4), ITERMVS_ERR_ALIGN);
-    // 16-bit storage is read with 16-byte lanes: every pixel vector starts on a 16-byte boundary
-    ITERMVS_RETURN_IF(s.dtype != ITERMVS_F32 && ((s.sx % 8) || (s.sy % 8) || (s.sb % 8)), ITERMVS_ERR_ALIGN);
+// Argument checks of the fused correlation entry points (corr.hip, corr_bwd.hip): all of them run before the stream is touched.
+// The S source maps of one level as the kernels address them, whichever form the caller described them in.
+struct itermvs_level_desc {
+    const void* base[ITERMVS_MAX_SRC];   // direct form: the S views, then view 0 repeated; slot form: the slab in every entry
+    int64_t stride;                      // elements between batch items (direct form) or between slots
+    int64_t sc, sy, sx;
+    int C, H, W, dtype;
+    const int32_t* slot;                 // device [B,S] slot table, nullptr in the direct form
+    int n_slots;
+};
+
+// the rules both forms share
+static inline int itermvs_check_level(const itermvs_level_desc& d) {
+    ITERMVS_RETURN_IF(d.C != 16 && d.C != 32 && d.C != 48, ITERMVS_ERR_CHANNELS);
+    ITERMVS_RETURN_IF(d.H < 1 || d.W < 1, ITERMVS_ERR_DIMS);
+    ITERMVS_RETURN_IF(d.sc != 1, ITERMVS_ERR_LAYOUT);
+    ITERMVS_RETURN_IF(d.dtype < ITERMVS_F32 || d.dtype > ITERMVS_BF16, ITERMVS_ERR_DTYPE);
+    // every pixel vector starts on a 16-byte boundary (16-bit storage is read with 16-byte lanes)
+    const int64_t q = d.dtype == ITERMVS_F32 ? 4 : 8;
+    ITERMVS_RETURN_IF((d.sx % q) || (d.sy % q) || (d.stride % q), ITERMVS_ERR_ALIGN);
     // 32-bit BYTE offsets of the taps inside one view's map
-    ITERMVS_RETURN_IF(s.sx <= 0 || s.sy <= 0 || (int64_t)s.H * s.sy * (s.dtype == ITERMVS_F32 ? 4 : 2) >= (int64_t)1 << 32, ITERMVS_ERR_DIMS);
+    ITERMVS_RETURN_IF((int64_t)d.H * d.sy * (d.dtype == ITERMVS_F32 ? 4 : 2) >= (int64_t)1 << 32, ITERMVS_ERR_DIMS);
+    return ITERMVS_OK;
+}
+
+// direct form (itermvs_level_src): per-view pointers sharing one set of strides.  S is in 1 .. ITERMVS_MAX_SRC.
+static inline int itermvs_describe_level(itermvs_level_desc& d, const itermvs_level_src& s, int S) {
+    for (int v = 0; v < ITERMVS_MAX_SRC; ++v) d.base[v] = s.view[v < S ? v : 0];
+    d.stride = s.sb; d.sc = s.sc; d.sy = s.sy; d.sx = s.sx;
+    d.C = s.C; d.H = s.H; d.W = s.W; d.dtype = s.dtype;
+    d.slot = nullptr; d.n_slots = 0;
+    const int rc = itermvs_check_level(d);
+    if (rc) return rc;
+    ITERMVS_RETURN_IF(s.sx <= 0 || s.sy <= 0, ITERMVS_ERR_DIMS);
     for (int v = 0; v < S; ++v) {
         ITERMVS_RETURN_IF(!s.view[v], ITERMVS_ERR_NULL);
         ITERMVS_RETURN_IF(((uintptr_t)s.view[v]) % 16, ITERMVS_ERR_ALIGN);
@@ -467,19 +490,59 @@ static inline int itermvs_check_level(const itermvs_level_src& s, int S) {
     return ITERMVS_OK;
 }
 
-// argument checks of one level of the slot forms (itermvs_corr_iter_slots / itermvs_corr_init_slots)
-static inline int itermvs_check_slots(const itermvs_level_slots& s) {
+// slot form (itermvs_level_slots): one slab, view (b, s) = slot[b * S + s]
+static inline int itermvs_describe_level(itermvs_level_desc& d, const itermvs_level_slots& s, int /*S*/) {
     ITERMVS_RETURN_IF(!s.slab || !s.slot, ITERMVS_ERR_NULL);
-    ITERMVS_RETURN_IF(s.C != 16 && s.C != 32 && s.C != 48, ITERMVS_ERR_CHANNELS);
-    ITERMVS_RETURN_IF(s.H < 1 || s.W < 1 || s.n_slots < 1, ITERMVS_ERR_DIMS);
-    ITERMVS_RETURN_IF(s.sc != 1, ITERMVS_ERR_LAYOUT);
-    ITERMVS_RETURN_IF(s.dtype < ITERMVS_F32 || s.dtype > ITERMVS_BF16, ITERMVS_ERR_DTYPE);
+    for (int v = 0; v < ITERMVS_MAX_SRC; ++v) d.base[v] = s.slab;
+    d.stride = s.slot_stride; d.sc = s.sc; d.sy = s.sy; d.sx = s.sx;
+    d.C = s.C; d.H = s.H; d.W = s.W; d.dtype = s.dtype;
+    d.slot = s.slot; d.n_slots = s.n_slots;
+    const int rc = itermvs_check_level(d);
+    if (rc) return rc;
+    ITERMVS_RETURN_IF(s.n_slots < 1, ITERMVS_ERR_DIMS);
     ITERMVS_RETURN_IF(((uintptr_t)s.slab) % 16, ITERMVS_ERR_ALIGN);
-    const int64_t q = s.dtype == ITERMVS_F32 ? 4 : 8;          // 16-byte pixel vectors, as in itermvs_check_level
-    ITERMVS_RETURN_IF((s.sx % q) || (s.sy % q) || (s.slot_stride % q), ITERMVS_ERR_ALIGN);
     ITERMVS_RETURN_IF(s.sx < s.C || s.sy < (int64_t)s.W * s.sx, ITERMVS_ERR_LAYOUT);
     ITERMVS_RETURN_IF(s.slot_stride < (int64_t)s.H * s.sy, ITERMVS_ERR_LAYOUT);      // slots do not overlap
-    ITERMVS_RETURN_IF((int64_t)s.H * s.sy * (s.dtype == ITERMVS_F32 ? 4 : 2) >= (int64_t)1 << 32, ITERMVS_ERR_DIMS);
     return ITERMVS_OK;
 }
 
+// The parameter block of the iteration branch and its three levels (Src: itermvs_level_src or itermvs_level_slots).
+// `forward`: the output pointers are needed; the gradient entry point ignores them.
+template <class Src>
+static inline int itermvs_check_iter_params(const itermvs_corr_iter_params& p, const Src* src, bool forward,
+                                            itermvs_level_desc (&lv)[3]) {
+    ITERMVS_RETURN_IF(p.B < 1 || p.H < 1 || p.W < 1, ITERMVS_ERR_DIMS);
+    ITERMVS_RETURN_IF(p.S < 1 || p.S > ITERMVS_MAX_SRC, ITERMVS_ERR_VIEWS);
+    ITERMVS_RETURN_IF(!p.ref_q || !p.proj || !p.view_w || !p.inv_depth_min || !p.inv_depth_max, ITERMVS_ERR_NULL);
+    ITERMVS_RETURN_IF(((uintptr_t)p.ref_q) % 16, ITERMVS_ERR_ALIGN);
+    for (int l = 0; l < 3; ++l) {
+        const int rc = itermvs_describe_level(lv[l], src[l], p.S);
+        if (rc) return rc;
+        ITERMVS_RETURN_IF(p.N[l] < 1 || p.N[l] > ITERMVS_MAX_HYP, ITERMVS_ERR_DIMS);
+        ITERMVS_RETURN_IF(forward && !p.out[l], ITERMVS_ERR_NULL);
+        ITERMVS_RETURN_IF(!p.depth[l] && !p.norm_depth, ITERMVS_ERR_NULL);
+    }
+    // view_w strides: all 0 = contiguous [B,S,H,W]
+    ITERMVS_RETURN_IF((p.view_w_sb || p.view_w_ss || p.view_w_sp) && (p.view_w_ss < 1 || p.view_w_sp < 1 || p.view_w_sb < 0),
+                      ITERMVS_ERR_LAYOUT);
+    // One kernel form: source views walked inside the lane.  (A views-across-waves form issued 14 % fewer vector instructions but
+    // missed the vector L1 31 % more often -- 33.4 vs 28.9 us, profiles/r02 -- and was removed; `impl` is reserved.)
+    ITERMVS_RETURN_IF(p.impl != 0, ITERMVS_ERR_DIMS);
+    ITERMVS_RETURN_IF(lv[1].dtype != lv[0].dtype || lv[2].dtype != lv[0].dtype, ITERMVS_ERR_DTYPE);
+    return ITERMVS_OK;
+}
+
+// The parameter block of the initialisation branch and its level.
+template <class Src>
+static inline int itermvs_check_init_params(const itermvs_corr_init_params& p, const Src& src, bool forward, itermvs_level_desc& d) {
+    ITERMVS_RETURN_IF(p.B < 1 || p.H < 1 || p.W < 1 || p.N < 2, ITERMVS_ERR_DIMS);
+    ITERMVS_RETURN_IF(p.S < 1 || p.S > ITERMVS_MAX_SRC, ITERMVS_ERR_VIEWS);
+    ITERMVS_RETURN_IF(!p.ref.data || !p.proj || !p.inv_depth_min || !p.inv_depth_max || (forward && !p.out), ITERMVS_ERR_NULL);
+    const int rc = itermvs_describe_level(d, src, p.S);
+    if (rc) return rc;
+    ITERMVS_RETURN_IF(p.ref.C != d.C || p.ref.H != p.H || p.ref.W != p.W, forward ? ITERMVS_ERR_DIMS : ITERMVS_ERR_LAYOUT);
+    ITERMVS_RETURN_IF(p.ref.dtype != d.dtype, ITERMVS_ERR_DTYPE);
+    ITERMVS_RETURN_IF(p.out_layout != 0 && p.out_layout != 1, ITERMVS_ERR_LAYOUT);
+    ITERMVS_RETURN_IF(p.out_layout == 1 && ((uintptr_t)p.out) % 16, ITERMVS_ERR_ALIGN);
+    return ITERMVS_OK;
+}

@@ -6,6 +6,7 @@ CPU path: a CPU tensor raises ``RuntimeError``.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
@@ -246,29 +247,38 @@ def ref_quarter_compose(ref1: Tensor, ref2: Tensor, ref3: Tensor, mats: Tensor, 
     return out, proj, imin, imax
 
 
-def corr_iter(src: Dict[int, Sequence[Tensor]], ref_q: Tensor, proj: Tensor, view_w: Tensor,
-              inv_min: Tensor, inv_max: Tensor, depth: Optional[Dict[int, Tensor]] = None,
-              norm_depth: Optional[Tensor] = None, offsets: Optional[Dict[int, Sequence[float]]] = None,
-              out: Optional[List[Tensor]] = None, timed: bool = True) -> List[Tensor]:
-    """itermvs.py:84-120 fused (see include/itermvs_hip.h).  ``src[l]`` = S channels-last maps of
-    level l; ``proj`` [3,B,S,12]; ``view_w`` [B,S,H,W]; hypotheses either explicit
-    ``depth[l]`` [B,N_l,H,W] or generated from ``norm_depth`` [B,1,H,W] + ``offsets[l]``.
-    Returns the three aggregated group correlations [B,N_l,8,H,W]."""
+@contextlib.contextmanager
+def _untimed(bit: int):
+    """the launches inside carry no timing events (itermvs_profile_*): mask ``bit`` (0: none) is off, and back on however they end"""
+    lib = _lib.load()
+    if bit:
+        lib.itermvs_profile_set_mask(_PROFILE_MASK[0] & ~bit)
+    try:
+        yield
+    finally:
+        if bit:
+            lib.itermvs_profile_set_mask(_PROFILE_MASK[0])
+
+
+def _corr_iter_params(src, ref_q, proj, view_w, inv_min, inv_max, norm_depth, offsets, outs, depth=None, want_out=True):
+    """The parameter block of itermvs_corr_iter / _slots / _backward.  ``outs`` None: allocated here; ``want_out=False`` (the
+    backward): no output pointers.  The block carries what it points into: ``p.slots`` (the itermvs_level_slots of slot
+    sources, else None), ``p.outs``, ``p.norm_depth_tensor`` (as the kernel reads it), ``p.keep`` (copies made here)."""
     b, h, w, _ = ref_q.shape
-    slots = None
+    p = CorrIterParams()
+    p.slots = None
     if isinstance(src[1], SlotSource):          # scan mode: itermvs_corr_iter_slots
         if not all(isinstance(src[l], SlotSource) and src[l].B == b and src[l].S == src[1].S for l in (1, 2, 3)):
             raise RuntimeError("corr_iter: slot sources of all three levels must share the [B,S] table shape")
         s = src[1].S
-        slots = (LevelSlots * 3)(*[src[l].struct() for l in (1, 2, 3)])
+        p.slots = (LevelSlots * 3)(*[src[l].struct() for l in (1, 2, 3)])
     else:
         s = len(src[1])
-    p = CorrIterParams()
     p.B, p.S, p.H, p.W = b, s, h, w
     keep = []
-    outs: List[Tensor] = []
+    p.outs = []
     for i, l in enumerate((1, 2, 3)):
-        if slots is None:
+        if p.slots is None:
             p.src[i] = level_src(src[l], f"src level {l}")
         if depth is not None and depth.get(l) is not None:
             d = _dev(depth[l], "depth").contiguous()
@@ -285,9 +295,10 @@ def corr_iter(src: Dict[int, Sequence[Tensor]], ref_q: Tensor, proj: Tensor, vie
         if n > MAX_HYP:
             raise RuntimeError(f"corr_iter: at most {MAX_HYP} hypotheses per level")
         p.N[i] = n
-        o = out[i] if out is not None else torch.empty((b, n, 8, h, w), device=ref_q.device, dtype=torch.float32)
-        outs.append(o)
-        p.out[i] = o.data_ptr()
+        if want_out:
+            o = outs[i] if outs is not None else torch.empty((b, n, 8, h, w), device=ref_q.device, dtype=torch.float32)
+            p.outs.append(o)
+            p.out[i] = o.data_ptr()
     if norm_depth is not None:
         # [B,1,H,W] view, possibly one channel of a wider contiguous [B,Ct,H,W] buffer
         _dev(norm_depth, "norm_depth")
@@ -295,6 +306,7 @@ def corr_iter(src: Dict[int, Sequence[Tensor]], ref_q: Tensor, proj: Tensor, vie
             norm_depth = norm_depth.contiguous()
         p.norm_depth = norm_depth.data_ptr()
         p.norm_depth_sb = norm_depth.stride(0)
+    p.norm_depth_tensor = norm_depth
     proj = _dev(proj, "proj").contiguous()
     # [B,S,H,W] with any batch / view / pixel strides whose rows are dense in the pixel stride: contiguous, or the
     # interleaved [B,H,W,S] storage view_aggregate_up(interleaved=True) returns (one vector load per lane quad)
@@ -303,38 +315,37 @@ def corr_iter(src: Dict[int, Sequence[Tensor]], ref_q: Tensor, proj: Tensor, vie
         raise RuntimeError(f"corr_iter: view_w must be [B,S,H,W] = {(b, s, h, w)}, got {tuple(view_w.shape)}")
     if view_w.dtype != torch.float32 or view_w.stride(2) != w * view_w.stride(3) or min(view_w.stride()) < 1:
         view_w = view_w.float().contiguous()
-    p.view_w_sb, p.view_w_ss, p.view_w_sp = view_w.stride(0), view_w.stride(1), view_w.stride(3)
+    # a contiguous tensor goes as the all-zero default: the stride of a size-1 dimension is arbitrary, and the backward
+    # takes nothing but the canonical contiguous strides
+    if not view_w.is_contiguous():
+        p.view_w_sb, p.view_w_ss, p.view_w_sp = view_w.stride(0), view_w.stride(1), view_w.stride(3)
     p.ref_q, p.proj, p.view_w = _dev(ref_q, "ref_q").data_ptr(), proj.data_ptr(), view_w.data_ptr()
     p.inv_depth_min, p.inv_depth_max = _dev(inv_min, "inv_min").data_ptr(), _dev(inv_max, "inv_max").data_ptr()
+    p.keep = (keep, proj, view_w)
+    return p
+
+
+def _launch_corr(name: str, p) -> None:
+    """itermvs_corr_iter / itermvs_corr_init (``name``) on block ``p``: the slot form when its sources are slot sources"""
     lib = _lib.load()
-    if not timed:               # no timing events around this launch (itermvs_profile_*): mask bit 0 off for the call
-        lib.itermvs_profile_set_mask(_PROFILE_MASK[0] & ~1)
-    if slots is None:
-        check(lib.itermvs_corr_iter(C.byref(p), _stream()), "itermvs_corr_iter")
+    if p.slots is None:
+        check(getattr(lib, name)(C.byref(p), _stream()), name)
     else:
-        check(lib.itermvs_corr_iter_slots(C.byref(p), slots, _stream()), "itermvs_corr_iter_slots")
-    if not timed:
-        lib.itermvs_profile_set_mask(_PROFILE_MASK[0])
-    return outs
+        check(getattr(lib, name + "_slots")(C.byref(p), p.slots, _stream()), name + "_slots")
 
 
-def _corr_iter_params(src, ref_q, proj, view_w, inv_min, inv_max, norm_depth, offsets, outs):
-    """parameter block of itermvs_corr_iter for hypotheses generated from ``norm_depth`` + ``offsets``; returns (block, keep-alive)"""
-    b, h, w, _ = ref_q.shape
-    p = CorrIterParams()
-    p.B, p.S, p.H, p.W = b, len(src[1]), h, w
-    for i, l in enumerate((1, 2, 3)):
-        p.src[i] = level_src(src[l], f"src level {l}")
-        p.depth[i] = None
-        p.N[i] = len(offsets[l])
-        for k, o in enumerate(offsets[l]):
-            p.offsets[i][k] = o
-        p.out[i] = outs[i].data_ptr() if outs is not None else None
-    nd = norm_depth if (norm_depth.stride(3) == 1 and norm_depth.stride(2) == w) else norm_depth.contiguous()
-    p.norm_depth, p.norm_depth_sb = nd.data_ptr(), nd.stride(0)
-    p.ref_q, p.proj, p.view_w = ref_q.data_ptr(), proj.data_ptr(), view_w.data_ptr()
-    p.inv_depth_min, p.inv_depth_max = inv_min.data_ptr(), inv_max.data_ptr()
-    return p, nd
+def corr_iter(src: Dict[int, Sequence[Tensor]], ref_q: Tensor, proj: Tensor, view_w: Tensor,
+              inv_min: Tensor, inv_max: Tensor, depth: Optional[Dict[int, Tensor]] = None,
+              norm_depth: Optional[Tensor] = None, offsets: Optional[Dict[int, Sequence[float]]] = None,
+              out: Optional[List[Tensor]] = None, timed: bool = True) -> List[Tensor]:
+    """itermvs.py:84-120 fused (see include/itermvs_hip.h).  ``src[l]`` = S channels-last maps of
+    level l; ``proj`` [3,B,S,12]; ``view_w`` [B,S,H,W]; hypotheses either explicit
+    ``depth[l]`` [B,N_l,H,W] or generated from ``norm_depth`` [B,1,H,W] + ``offsets[l]``.
+    Returns the three aggregated group correlations [B,N_l,8,H,W]."""
+    p = _corr_iter_params(src, ref_q, proj, view_w, inv_min, inv_max, norm_depth, offsets, out, depth)
+    with _untimed(0 if timed else 1):
+        _launch_corr("itermvs_corr_iter", p)
+    return p.outs
 
 
 def _views(feat: Tensor, b: int, v: int):
@@ -419,13 +430,11 @@ class _CorrIterFn(torch.autograd.Function):
         ctx.pool = pool
         f1, f2, f3 = s1, s2, s3
         src = {l: _views(f, b, v)[1] for l, f in ((1, f1), (2, f2), (3, f3))}
-        _, h, w, _ = ref_q.shape
-        outs = [torch.empty((b, len(offsets[l]), 8, h, w), device=ref_q.device, dtype=torch.float32) for l in (1, 2, 3)]
-        p, nd = _corr_iter_params(src, ref_q, proj, view_w, inv_min, inv_max, norm_depth, offsets, outs)
-        check(_lib.load().itermvs_corr_iter(C.byref(p), _stream()), "itermvs_corr_iter")
-        ctx.save_for_backward(ref_q, proj, view_w, inv_min, inv_max, nd, f1, f2, f3)
+        p = _corr_iter_params(src, ref_q, proj, view_w, inv_min, inv_max, norm_depth, offsets, None)
+        _launch_corr("itermvs_corr_iter", p)
+        ctx.save_for_backward(ref_q, proj, view_w, inv_min, inv_max, p.norm_depth_tensor, f1, f2, f3)
         ctx.meta = (offsets, b, v)
-        return tuple(outs)
+        return tuple(p.outs)
 
     @staticmethod
     def backward(ctx, *gouts):
@@ -433,7 +442,7 @@ class _CorrIterFn(torch.autograd.Function):
         offsets, b, v = ctx.meta
         feats = (f1, f2, f3)
         src = {l: _views(f, b, v)[1] for l, f in zip((1, 2, 3), feats)}
-        p, nd = _corr_iter_params(src, ref_q, proj, view_w, inv_min, inv_max, nd, offsets, None)
+        p = _corr_iter_params(src, ref_q, proj, view_w, inv_min, inv_max, nd, offsets, None, want_out=False)
         gouts = [g.contiguous() for g in gouts]
         # dense channels-last like the features, fp32 whatever their storage type (fp32 atomics); with a pool: the step's
         # shared accumulators (FeatureGradPool), handed to autograd once by the sink
@@ -464,16 +473,44 @@ def corr_iter_train(feats: Dict[int, Tensor], b: int, v: int, ref_q: Tensor, pro
                              inv_min, inv_max, norm_depth.detach(), {l: tuple(offsets[l]) for l in (1, 2, 3)}, b, v, *f, *st, pool)
 
 
-def _corr_init_params(src3, ref3, proj, inv_min, inv_max, n, out):
+def _corr_init_params(src3, ref3, proj, inv_min, inv_max, n, out, depth=None, groups_last=None):
+    """The parameter block of itermvs_corr_init / _slots / _backward.  ``out`` None: no output (the backward), or, with
+    ``groups_last`` False / True, allocated here in that layout.  Carries ``p.slots``, ``p.out_tensor``, ``p.keep`` likewise."""
     b, _, h, w = ref3.shape
     p = CorrInitParams()
-    p.B, p.S, p.H, p.W, p.N = b, len(src3), h, w, n
-    p.src = level_src(src3, "src level 3")
+    p.slots = None
+    if isinstance(src3, SlotSource):            # scan mode: itermvs_corr_init_slots
+        if src3.B != b:
+            raise RuntimeError("corr_init: the slot table must have one row per batch item")
+        s, p.slots = src3.S, (LevelSlots * 1)(src3.struct())
+    else:
+        s = len(src3)
+    p.B, p.S, p.H, p.W, p.N = b, s, h, w, n
+    if p.slots is None:
+        p.src = level_src(src3, "src level 3")
     p.ref = fmap(ref3, "ref3")
+    proj = _dev(proj, "proj").contiguous()
     p.proj = proj.data_ptr()
-    p.depth = None
-    p.inv_depth_min, p.inv_depth_max = inv_min.data_ptr(), inv_max.data_ptr()
-    p.out = out.data_ptr() if out is not None else None
+    if depth is not None:
+        depth = _dev(depth, "depth").contiguous()
+        p.N = depth.shape[1]
+        p.depth = depth.data_ptr()
+    p.inv_depth_min, p.inv_depth_max = _dev(inv_min, "inv_min").data_ptr(), _dev(inv_max, "inv_max").data_ptr()
+    if out is None and groups_last is not None:
+        out = torch.empty((b, s, p.N, h, w, 8) if groups_last else (b, s, p.N, 8, h, w), device=ref3.device, dtype=torch.float32)
+        out = out.permute(0, 1, 2, 5, 3, 4) if groups_last else out
+    if out is not None:
+        if tuple(out.shape) != (b, s, p.N, 8, h, w) or out.dtype != torch.float32:
+            raise RuntimeError(f"corr_init: out must be float32 [B,S,N,8,H,W] = {(b, s, p.N, 8, h, w)}")
+        if out.is_contiguous():
+            p.out_layout = 0
+        elif out.permute(0, 1, 2, 4, 5, 3).is_contiguous():
+            p.out_layout = 1
+        else:
+            raise RuntimeError("corr_init: out must be contiguous [B,S,N,8,H,W] or the view of contiguous [B,S,N,H,W,8] storage")
+        p.out = out.data_ptr()
+    p.out_tensor = out
+    p.keep = (proj, depth)
     return p
 
 
@@ -486,12 +523,11 @@ class _CorrInitFn(torch.autograd.Function):
         ctx.pool = pool
         f3 = s3                 # the tensor the kernel reads (f3 itself, or its 16-bit rounding); gradient goes to f3 in fp32
         ref3, src3 = _views(f3, b, v)
-        out = torch.empty((b, v - 1, n, 8) + tuple(f3.shape[2:]), device=f3.device, dtype=torch.float32)
-        p = _corr_init_params(src3, ref3, proj, inv_min, inv_max, n, out)
-        check(_lib.load().itermvs_corr_init(C.byref(p), _stream()), "itermvs_corr_init")
+        p = _corr_init_params(src3, ref3, proj, inv_min, inv_max, n, None, groups_last=False)
+        _launch_corr("itermvs_corr_init", p)
         ctx.save_for_backward(f3, proj, inv_min, inv_max)
         ctx.meta = (n, b, v)
-        return out
+        return p.out_tensor
 
     @staticmethod
     def backward(ctx, gout):
@@ -594,50 +630,10 @@ def corr_init(src3: Sequence[Tensor], ref3: Tensor, proj: Tensor, inv_min: Tenso
     """itermvs.py:48-51 (+ :11-19): per-view group correlation, [B,S,N,8,H,W].  ``groups_last``: STORED [B,S,N,H,W,8] and returned
     as the [B,S,N,8,H,W] view of that storage -- as [B*S*N,8,H,W] it is a channels-last tensor, which conv2d's 8-channel bf16x3
     layer stages with two 16-byte loads per pixel, and view_aggregate(_up) reads it as it is."""
-    b, _, h, w = ref3.shape
-    slots = None
-    if isinstance(src3, SlotSource):            # scan mode: itermvs_corr_init_slots
-        if src3.B != b:
-            raise RuntimeError("corr_init: the slot table must have one row per batch item")
-        s, slots = src3.S, src3.struct()
-    else:
-        s = len(src3)
-    p = CorrInitParams()
-    p.B, p.S, p.H, p.W, p.N = b, s, h, w, num_samples
-    if slots is None:
-        p.src = level_src(src3, "src level 3")
-    p.ref = fmap(ref3, "ref3")
-    proj = _dev(proj, "proj").contiguous()
-    p.proj = proj.data_ptr()
-    if depth is not None:
-        depth = _dev(depth, "depth").contiguous()
-        p.N = depth.shape[1]
-        p.depth = depth.data_ptr()
-    p.inv_depth_min, p.inv_depth_max = _dev(inv_min, "inv_min").data_ptr(), _dev(inv_max, "inv_max").data_ptr()
-    if out is None:
-        if groups_last:
-            out = torch.empty((b, s, p.N, h, w, 8), device=ref3.device, dtype=torch.float32).permute(0, 1, 2, 5, 3, 4)
-        else:
-            out = torch.empty((b, s, p.N, 8, h, w), device=ref3.device, dtype=torch.float32)
-    if tuple(out.shape) != (b, s, p.N, 8, h, w) or out.dtype != torch.float32:
-        raise RuntimeError(f"corr_init: out must be float32 [B,S,N,8,H,W] = {(b, s, p.N, 8, h, w)}")
-    if out.is_contiguous():
-        p.out_layout = 0
-    elif out.permute(0, 1, 2, 4, 5, 3).is_contiguous():
-        p.out_layout = 1
-    else:
-        raise RuntimeError("corr_init: out must be contiguous [B,S,N,8,H,W] or the view of contiguous [B,S,N,H,W,8] storage")
-    p.out = out.data_ptr()
-    lib = _lib.load()
-    if not timed:               # no timing events around this launch: mask bit 1 off for the call
-        lib.itermvs_profile_set_mask(_PROFILE_MASK[0] & ~2)
-    if slots is None:
-        check(lib.itermvs_corr_init(C.byref(p), _stream()), "itermvs_corr_init")
-    else:
-        check(lib.itermvs_corr_init_slots(C.byref(p), C.byref(slots), _stream()), "itermvs_corr_init_slots")
-    if not timed:
-        lib.itermvs_profile_set_mask(_PROFILE_MASK[0])
-    return out
+    p = _corr_init_params(src3, ref3, proj, inv_min, inv_max, num_samples, out, depth, groups_last=bool(groups_last))
+    with _untimed(0 if timed else 2):
+        _launch_corr("itermvs_corr_init", p)
+    return p.out_tensor
 
 
 def tap_indices(proj: Tensor, inv_min: Tensor, inv_max: Tensor, grid_hw: Tuple[int, int], src_hw: Tuple[int, int], *,

@@ -365,6 +365,57 @@ def test_corr_iter_backward_matches_autograd(b, v, dtype):
     assert maxdiff(rq.grad, ref_q.grad) <= 1e-4 * max(1.0, float(ref_q.grad.abs().max()))
 
 
+def test_corr_iter_train_view_w_odd_batch_stride():
+    """a contiguous [1,S,H,W] view_w may carry any stride on its size-1 batch dimension: forward and backward read it like
+    its canonical clone (the backward entry point takes the default or exactly the canonical strides, nothing else)"""
+    from itermvs_amd.engine import sample_offsets
+    b, v, h, w = 1, 3, 24, 40
+    gen, feats, sizes, chans, p12, inv_min, inv_max = _bwd_case(b, v, h, w, 7)
+    ref_q = torch.randn((b, h, w, 96), generator=gen)
+    nd = torch.rand((b, 1, h, w), generator=gen)
+    gw = [cu(torch.randn((b, n, 8, h, w), generator=gen)) for n in (4, 4, 2)]
+    vw = cu(torch.rand((b, v - 1, h, w), generator=gen))
+    odd = torch.as_strided(vw, vw.shape, (7, h * w, w, 1))
+    assert odd.is_contiguous() and odd.stride(0) == 7 and torch.equal(odd, vw)
+    res = []
+    for view_w in (vw.clone(), odd):
+        fg = {l: cu(feats[l].detach()).contiguous(memory_format=torch.channels_last).requires_grad_(True) for l in (1, 2, 3)}
+        rq = cu(ref_q).requires_grad_(True)
+        outs = ops().corr_iter_train(fg, b, v, rq, cu(p12), view_w, cu(inv_min), cu(inv_max), cu(nd), sample_offsets())
+        sum((o * g).sum() for o, g in zip(outs, gw)).backward()
+        res.append((outs, [fg[l].grad for l in (1, 2, 3)] + [rq.grad]))
+    for o_ref, o in zip(res[0][0], res[1][0]):
+        assert torch.equal(o_ref, o)
+    for g_ref, g in zip(res[0][1], res[1][1]):
+        assert maxdiff(g, g_ref) <= 1e-4 * max(1.0, float(g_ref.abs().max()))
+
+
+def test_untimed_launch_that_raises_restores_the_profile_mask():
+    """corr_iter(timed=False) switches its profile-mask bit off for the call; a launch that raises must switch it back on"""
+    o = ops()
+    b, s, h, w = 1, 2, 24, 40
+    gen = torch.Generator().manual_seed(3)
+
+    def maps(c, hh, ww):
+        return [cu(torch.randn((b, c, hh, ww), generator=gen)).contiguous(memory_format=torch.channels_last) for _ in range(s)]
+    src = {1: maps(16, 2 * h, 2 * w), 2: maps(32, h, w), 3: maps(48, h // 2, w // 2)}
+    p12 = _bwd_case(b, s + 1, h, w, 7)[4]
+    args = (cu(torch.randn((b, h, w, 96), generator=gen)), cu(p12), cu(torch.rand((b, s, h, w), generator=gen)),
+            cu(torch.full((b,), 1 / 425.0)), cu(torch.full((b,), 1 / 935.0)))
+    kw = dict(norm_depth=cu(torch.rand((b, 1, h, w), generator=gen)), offsets={1: (-0.1, 0.0, 0.1, 0.2), 2: (-0.1, 0.0, 0.1, 0.2), 3: (0.0, 0.1)})
+    bad = {**src, 2: maps(20, h, w)}
+    try:
+        for enabled_before in (False, True):       # the second round: the first round's profile_enable cannot be what restores it
+            with pytest.raises(RuntimeError, match="channel"):
+                o.corr_iter(bad, *args, timed=False, **kw)
+            if not enabled_before:
+                o.profile_enable(16)
+            o.corr_iter(src, *args, **kw)
+            assert [k for k, _ in o.profile_collect()] == [1]
+    finally:
+        o.profile_enable(0)
+
+
 @pytest.mark.parametrize("cams", ["regular", "vanishing_line", "singular"])
 @pytest.mark.parametrize("b,v", [(1, 3), (2, 5)])
 def test_corr_init_backward_matches_autograd(b, v, cams):
