@@ -49,7 +49,8 @@ typedef enum itermvs_status {
     ITERMVS_ERR_ALIGN = -5,       /* pointer / stride not aligned for vector path */
     ITERMVS_ERR_LAYOUT = -6,      /* fused kernels need channels-last features    */
     ITERMVS_ERR_LAUNCH = -7,      /* hipLaunchKernel failed (see hipGetLastError) */
-    ITERMVS_ERR_DTYPE = -8        /* feature storage type not supported by this entry point */
+    ITERMVS_ERR_DTYPE = -8,       /* feature storage type not supported by this entry point */
+    ITERMVS_ERR_MODEL = -9        /* camera model not supported by itermvs_undistort_rgb8 (FOV, THIN_PRISM_FISHEYE, unknown id) */
 } itermvs_status;
 
 /* Storage type of FEATURE maps (the pyramids the correlation kernels gather from).  Arithmetic is always fp32: 16-bit
@@ -807,6 +808,40 @@ int itermvs_image_pyramid(const uint8_t* src, int32_t V, int32_t Hs, int32_t Ws,
 int itermvs_resize_rgb8(const uint8_t* src, int32_t V, int32_t Hs, int32_t Ws, int32_t H, int32_t W, const int32_t* xbounds,
                         const int32_t* xk, int32_t KX, const int32_t* ybounds, const int32_t* yk, int32_t KY, uint8_t* out,
                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * itermvs_undistort_rgb8 -- one image of a COLMAP camera with lens distortion resampled to a pinhole camera (what COLMAP's
+ * image_undistorter does before dense stereo; colmap_input.py leaves it to the user).  One launch per image.
+ *   src [Hs,Ws,3] uint8 (device) -> out [Ho,Wo,3] uint8 (device); map [Ho,Wo,2] float64 (device) or NULL: (sx, sy) of every
+ *   output pixel as computed below, filled or not -- the kernel's sampling decisions, for the tests.
+ *   model: COLMAP's camera model id; params: its n_params parameters in COLMAP's order (HOST doubles, copied into the launch);
+ *   fx_o, fy_o, cx_o, cy_o: the output pinhole camera.
+ * Per output pixel (x, y), all in float64, one rounding per written operation (no fused multiply-add), COLMAP's pixel-centre
+ * convention (pixel (0, 0) covers [0, 1) x [0, 1)):
+ *   u = ((x + 0.5) - cx_o) / fx_o,  v = ((y + 0.5) - cy_o) / fy_o
+ *   u2 = u*u, v2 = v*v, r2 = u2 + v2, r4 = r2*r2, r6 = r4*r2, uv = u*v          (du, dv) by model:
+ *     0 SIMPLE_PINHOLE (f cx cy), 1 PINHOLE (fx fy cx cy):  du = dv = 0
+ *     2 SIMPLE_RADIAL (f cx cy k):            radial = k*r2;            du = u*radial
+ *     3 RADIAL (f cx cy k1 k2):               radial = k1*r2 + k2*r4;   du = u*radial
+ *     4 OPENCV (fx fy cx cy k1 k2 p1 p2):     radial as RADIAL;  du = (u*radial + (2*p1)*uv) + p2*(r2 + 2*u2)
+ *                                                                dv = (v*radial + (2*p2)*uv) + p1*(r2 + 2*v2)
+ *     6 FULL_OPENCV (.. k1 k2 p1 p2 k3 k4 k5 k6):  radial = (((1 + k1*r2) + k2*r4) + k3*r6) / (((1 + k4*r2) + k5*r4) + k6*r6);
+ *                                                  du = OPENCV's expression - u
+ *     8 SIMPLE_RADIAL_FISHEYE (f cx cy k), 9 RADIAL_FISHEYE (f cx cy k1 k2), 5 OPENCV_FISHEYE (fx fy cx cy k1 k2 k3 k4):
+ *       r = sqrt(r2); r > 2^-52:  t = atan(r), t2 = t*t, t4 = t2*t2, t6 = t4*t2, t8 = t4*t4,
+ *       td = t * (1 + k*t2) | t * ((1 + k1*t2) + k2*t4) | t * ((((1 + k1*t2) + k2*t4) + k3*t6) + k4*t8),
+ *       du = (u*td)/r - u;  otherwise du = dv = 0            (dv: v in u's place throughout)
+ *   sx = (fx*(u + du) + cx) - 0.5,  sy = (fy*(v + dv) + cy) - 0.5               (f for fx and fy in the one-focal models)
+ *   filled = sx >= 0 && sx <= Ws - 1 && sy >= 0 && sy <= Hs - 1   (NaN and +-Inf fail); not filled: the pixel is (0, 0, 0) and no
+ *   index is formed.  Filled: x0 = floor(sx), x1 = min(x0 + 1, Ws - 1), wx = sx - x0, rows likewise, and per channel
+ *   value = (1 - wy) * ((1 - wx)*p[y0][x0] + wx*p[y0][x1]) + wy * ((1 - wx)*p[y1][x0] + wx*p[y1][x1]),
+ *   out = min(max(floor(value + 0.5), 0), 255).
+ * Before the launch: ITERMVS_ERR_NULL (src, out or params NULL), ITERMVS_ERR_MODEL (7 FOV, 10 THIN_PRISM_FISHEYE, unknown id),
+ * ITERMVS_ERR_DIMS (a size < 1, n_params not the model's count, more than 2^31 - 1 workgroups).
+ * ------------------------------------------------------------------------------------------ */
+int itermvs_undistort_rgb8(const uint8_t* src, int32_t Hs, int32_t Ws, int32_t model, const double* params, int32_t n_params,
+                           double fx_o, double fy_o, double cx_o, double cy_o, int32_t Ho, int32_t Wo, uint8_t* out, double* map,
+                           void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Training input side (csrc/train_input.hip).

@@ -163,6 +163,8 @@ PROTOTYPES = {
     "itermvs_image_pyramid": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 5),
     "itermvs_resize_rgb8": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                                                  C.c_int32, C.c_void_p, C.c_void_p]),
+    "itermvs_undistort_rgb8": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_int32] +
+                               [C.c_double] * 4 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "itermvs_image_pyramid_jitter": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 7),
     "itermvs_gt_pyramid": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 6 + [C.c_void_p] * 9),
     "itermvs_bn_workspace_floats": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),

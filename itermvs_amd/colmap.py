@@ -407,23 +407,97 @@ def write_outputs(output_folder: str, model: Model, extrinsic: np.ndarray, score
         f.write(pair_text(select_views(score, num_src_images)))
 
 
+def copy_image(src: str, dst: str, convert_format: bool = False) -> None:
+    if convert_format:
+        from PIL import Image as PILImage
+        with PILImage.open(src) as img:
+            img.convert("RGB").save(dst, format="JPEG", quality=95)
+    elif os.path.abspath(src) != os.path.abspath(dst):
+        shutil.copyfile(src, dst)
+
+
 def copy_images(image_dir: str, renamed_dir: str, images: List[Image], convert_format: bool = False) -> None:
     """colmap_input.py:400-406: ``images/<name>`` -> ``images/%08d.jpg``; ``convert_format`` re-encodes as JPEG (Pillow)"""
     os.makedirs(renamed_dir, exist_ok=True)
     for i, im in enumerate(images):
-        src, dst = os.path.join(image_dir, im.name), os.path.join(renamed_dir, "%08d.jpg" % i)
-        if convert_format:
-            from PIL import Image as PILImage
-            with PILImage.open(src) as img:
-                img.convert("RGB").save(dst, format="JPEG", quality=95)
-        elif os.path.abspath(src) != os.path.abspath(dst):
-            shutil.copyfile(src, dst)
+        copy_image(os.path.join(image_dir, im.name), os.path.join(renamed_dir, "%08d.jpg" % i), convert_format)
+
+
+MAX_WORKERS = 16
+
+
+def undistort_images(image_dir: str, renamed_dir: str, model: Model, out_cameras: Dict[int, Camera], convert_format: bool = False,
+                     device="cuda", num_workers: int = 4, info: Optional[dict] = None) -> None:
+    """``images/<name>`` -> ``images/%08d.jpg`` as the pinhole cameras ``out_cameras`` (camera id -> undistort.undistorted_camera)
+    see them: decoded in a thread pool, uploaded as uint8, resampled by ``itermvs_undistort_rgb8``, downloaded and written as JPEG
+    of quality 95 in the same pool.  Images of a camera that ``out_cameras`` returns unchanged (no distortion) are copied as
+    :func:`copy_images` does.  ``info`` receives the seconds spent decoding, on the device (upload to download) and encoding,
+    the first and the last summed over the pool's threads."""
+    import time
+    from collections import deque
+    from concurrent.futures import ThreadPoolExecutor
+    from itertools import islice
+    import torch
+    from PIL import Image as PILImage
+    from . import ops
+    os.makedirs(renamed_dir, exist_ok=True)
+    workers = max(1, min(int(num_workers), MAX_WORKERS))
+    dev = torch.device(device)
+    spent = {"decode": 0.0, "device": 0.0, "encode": 0.0}
+
+    def decode(i: int) -> np.ndarray:
+        t0 = time.perf_counter()
+        im = model.images[i]
+        with PILImage.open(os.path.join(image_dir, im.name)) as img:
+            raw = np.array(img.convert("RGB"))
+        cam = model.cameras[im.camera_id]
+        if raw.shape[:2] != (cam.height, cam.width):
+            raise ValueError(f"image {i} ({im.name}) is {raw.shape[1]} x {raw.shape[0]}, its camera {cam.id} is {cam.width} x {cam.height}")
+        spent["decode"] += time.perf_counter() - t0          # (float adds under the interpreter lock: a statistic, not a ledger)
+        return raw
+
+    def encode(i: int, rgb: np.ndarray) -> None:
+        t0 = time.perf_counter()
+        PILImage.fromarray(rgb).save(os.path.join(renamed_dir, "%08d.jpg" % i), format="JPEG", quality=95)
+        spent["encode"] += time.perf_counter() - t0
+
+    warped = [i for i, im in enumerate(model.images) if out_cameras[im.camera_id] is not model.cameras[im.camera_id]]
+    for i, im in enumerate(model.images):
+        if out_cameras[im.camera_id] is model.cameras[im.camera_id]:
+            copy_image(os.path.join(image_dir, im.name), os.path.join(renamed_dir, "%08d.jpg" % i), convert_format)
+    with ThreadPoolExecutor(workers) as pool:
+        decoded, written, ahead = deque(), [], iter(warped)
+
+        def decode_more(n: int) -> None:                     # at most 2 x workers decoded images wait for the device
+            for j in islice(ahead, n):
+                decoded.append((j, pool.submit(decode, j)))
+
+        decode_more(2 * workers)
+        while decoded:
+            i, job = decoded.popleft()
+            raw = job.result()
+            decode_more(1)
+            t0 = time.perf_counter()
+            cam, out = model.cameras[model.images[i].camera_id], out_cameras[model.images[i].camera_id]
+            rgb = ops.undistort_rgb8(torch.from_numpy(raw).to(dev), cam.model, cam.params, out.params, (out.height, out.width))
+            rgb = rgb.cpu().numpy()                           # the download synchronises
+            spent["device"] += time.perf_counter() - t0
+            written.append(pool.submit(encode, i, rgb))
+        for job in written:
+            job.result()
+    if info is not None:
+        info.update(undistort_decode_s=spent["decode"], undistort_device_s=spent["device"], undistort_encode_s=spent["encode"],
+                    undistort_images=len(warped))
 
 
 def convert(input_folder: str, output_folder: Optional[str] = None, num_src_images: int = -1, theta0: float = 5, sigma1: float = 1,
-            sigma2: float = 10, convert_format: bool = False, device="cuda", info: Optional[dict] = None) -> None:
+            sigma2: float = 10, convert_format: bool = False, device="cuda", info: Optional[dict] = None, undistort: bool = False,
+            blank_pixels: float = 0.0, min_scale: float = 0.2, max_scale: float = 2.0, num_workers: int = 4) -> None:
     """``<input>/sparse`` + ``<input>/images`` -> ``<output>/cams_1``, ``<output>/images``, ``<output>/pair.txt``
-    (``output_folder`` None or empty: the input folder, like the reference).  ``info`` receives the stages' wall times."""
+    (``output_folder`` None or empty: the input folder, like the reference).  ``info`` receives the stages' wall times.
+    ``undistort``: every camera with lens distortion is replaced by the pinhole camera of ``undistort.undistorted_camera``
+    (``blank_pixels``, ``min_scale``, ``max_scale``: its options) in the cam files, and its images are resampled to it on the GPU
+    (:func:`undistort_images`); ``pair.txt`` and the depth ranges do not depend on the images and stay as they are."""
     import time
     if not output_folder:
         output_folder = input_folder
@@ -439,11 +513,25 @@ def convert(input_folder: str, output_folder: Optional[str] = None, num_src_imag
     extrinsic = extrinsic_matrices(model.images)
     score, ranges = device_scores_and_ranges(model, extrinsic, theta0, sigma1, sigma2, device)
     t2 = time.perf_counter()
-    write_outputs(output_folder, model, extrinsic, score, ranges, num_src_images)
-    copy_images(os.path.join(input_folder, "images"), os.path.join(output_folder, "images"), model.images, convert_format)
-    t3 = time.perf_counter()
+    t3 = t2
+    if undistort:
+        from .undistort import undistorted_camera
+        out_cameras = {cid: undistorted_camera(c, blank_pixels, min_scale, max_scale) for cid, c in model.cameras.items()}
+        write_outputs(output_folder, Model(out_cameras, model.images, model.point_ids, model.xyz), extrinsic, score, ranges,
+                      num_src_images)
+        t3 = time.perf_counter()
+        undistort_images(os.path.join(input_folder, "images"), os.path.join(output_folder, "images"), model, out_cameras,
+                         convert_format, device, num_workers, info)
+    else:
+        write_outputs(output_folder, model, extrinsic, score, ranges, num_src_images)
+        copy_images(os.path.join(input_folder, "images"), os.path.join(output_folder, "images"), model.images, convert_format)
+    t4 = time.perf_counter()
     if info is not None:
-        info.update(read_s=t1 - t0, device_s=t2 - t1, write_s=t3 - t2, images=len(model.images), points=len(model.point_ids))
+        if undistort:
+            info.update(read_s=t1 - t0, device_s=t2 - t1, write_s=t3 - t2, undistort_s=t4 - t3)
+        else:
+            info.update(read_s=t1 - t0, device_s=t2 - t1, write_s=t4 - t2)
+        info.update(images=len(model.images), points=len(model.point_ids))
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -457,9 +545,17 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--sigma2", type=float, default=10)
     p.add_argument("--convert_format", action="store_true", default=False, help="If set, convert image to jpg format.")
     p.add_argument("--device", type=str, default="cuda", help="device of the score / depth-range kernels")
+    p.add_argument("--undistort", action="store_true", default=False,
+                   help="resample the images of cameras with lens distortion to pinhole cameras on the GPU and write those cameras")
+    p.add_argument("--blank_pixels", type=float, default=0.0, help="--undistort: 0 crops to pixels the source covers, 1 keeps all of it")
+    p.add_argument("--min_scale", type=float, default=0.2, help="--undistort: lower bound of the per-axis change of the image size")
+    p.add_argument("--max_scale", type=float, default=2.0, help="--undistort: upper bound of the per-axis change of the image size")
+    p.add_argument("--num_workers", type=int, default=4, help="--undistort: threads that decode and encode images (at most 16)")
     return p
 
 
 def main(argv=None) -> None:
     a = build_parser().parse_args(argv)
-    convert(a.input_folder, a.output_folder, a.num_src_images, a.theta0, a.sigma1, a.sigma2, a.convert_format, a.device)
+    convert(a.input_folder, a.output_folder, a.num_src_images, a.theta0, a.sigma1, a.sigma2, a.convert_format, a.device,
+            undistort=a.undistort, blank_pixels=a.blank_pixels, min_scale=a.min_scale, max_scale=a.max_scale,
+            num_workers=a.num_workers)

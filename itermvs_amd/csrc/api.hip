@@ -18,6 +18,7 @@ extern "C" const char* itermvs_error_string(int status) {
         case ITERMVS_ERR_LAYOUT: return "fused kernels need channels-last feature maps (channel stride 1)";
         case ITERMVS_ERR_LAUNCH: return "HIP kernel launch failed";
         case ITERMVS_ERR_DTYPE: return "feature storage type not supported by this entry point";
+        case ITERMVS_ERR_MODEL: return "camera model not supported (FOV, THIN_PRISM_FISHEYE or an unknown model id)";
         default: return "unknown itermvs status";
     }
 }

@@ -1860,6 +1860,35 @@ def resize_rgb8(raw: Tensor, height: int, width: int) -> Tensor:
     return out
 
 
+def undistort_rgb8(raw: Tensor, model, params, out_camera, out_hw: Tuple[int, int], want_map: bool = False):
+    """itermvs_undistort_rgb8: raw [Hs,Ws,3] uint8 RGB (device), an image of the COLMAP camera (``model``: name or id, ``params``
+    in COLMAP's order) -> uint8 [Ho,Wo,3], the image of the pinhole camera ``out_camera`` = (fx, fy, cx, cy) of size ``out_hw``
+    = (Ho, Wo); pixels whose source coordinate leaves the image are (0, 0, 0).  ``want_map``: also float64 [Ho,Wo,2], the source
+    coordinates (sx, sy) the kernel sampled at.  FOV and THIN_PRISM_FISHEYE are a ValueError naming the model."""
+    from .colmap import CAMERA_MODELS, CAMERA_MODEL_NAMES
+    from .undistort import SUPPORTED_MODELS
+    name = CAMERA_MODELS[model][0] if model in CAMERA_MODELS else model
+    if name not in CAMERA_MODEL_NAMES or name not in SUPPORTED_MODELS:
+        raise ValueError(f"undistort_rgb8: camera model {name} is not supported")
+    mid, count = CAMERA_MODEL_NAMES[name]
+    values = [float(x) for x in params]
+    if len(values) != count:
+        raise ValueError(f"undistort_rgb8: camera model {name} has {count} parameters, got {len(values)}")
+    if not raw.is_cuda or raw.dtype != torch.uint8 or raw.dim() != 3 or raw.shape[2] != 3:
+        raise RuntimeError("undistort_rgb8: expected a CUDA uint8 tensor [Hs,Ws,3]")
+    height, width = int(out_hw[0]), int(out_hw[1])
+    if height < 1 or width < 1:
+        raise RuntimeError(f"undistort_rgb8: the output size must be positive, got {height} x {width}")
+    raw = raw.contiguous()
+    hs, ws, _ = raw.shape
+    fx, fy, cx, cy = (float(x) for x in out_camera)
+    out = torch.empty((height, width, 3), device=raw.device, dtype=torch.uint8)
+    coords = torch.empty((height, width, 2), device=raw.device, dtype=torch.float64) if want_map else None
+    check(_lib.load().itermvs_undistort_rgb8(raw.data_ptr(), hs, ws, mid, (C.c_double * count)(*values), count, fx, fy, cx, cy,
+                                             height, width, out.data_ptr(), _ptr(coords), _stream()), "itermvs_undistort_rgb8")
+    return (out, coords) if want_map else out
+
+
 JITTER_BYTES = 16      # sizeof(itermvs_jitter): brightness f32, contrast f32, contrast_first i32, enabled i32
 
 
