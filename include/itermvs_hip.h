@@ -392,6 +392,22 @@ int itermvs_res_chain16(const float* y1, int64_t y1_sn, const float* shortcut, i
                         int32_t H, int32_t W, const void* const* weights, const float* const* bias, float* out, int64_t out_sn, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * itermvs_down_conv -- the stride-2 pair of a FeatureNet residual block (models/net.py:14-15 `layer2`, `layer3`: the first
+ * ResidualBlock's conv1 and downsample read the same input, models/module.py:33-50; BatchNorm folded) in ONE launch:
+ *     y  = relu(conv3x3_s2(x; W1) + b1)          [N,C,Ho,Wo]
+ *     sc =      conv3x3_s2(x; Wd) + bd           [N,C,Ho,Wo]      padding 1, Ho = (H-1)/2 + 1, Wo = (W-1)/2 + 1
+ * A workgroup stages and splits each input tile once for all 2C output channels.  Arithmetic: the bf16x3 form of
+ * itermvs_conv2d's weight_format 3 (both operands split exactly into three bf16 terms, six cross products on
+ * v_mfma_f32_16x16x32_bf16, fp32 accumulation).
+ *   x [N,Cin,H,W] planes (image stride x_sn, elements); (Cin, C) = (16, 32) or (32, 48), anything else returns
+ *   ITERMVS_ERR_CHANNELS; w_packed: the weight of cat(W1, Wd) [2C,Cin,3,3] in weight_format 3 = bf16 [9][Cin/16][3][2C][16]
+ *   (itermvs_amd.ops.MfmaWeight(...).tile3), 16-byte aligned; bias: 2C floats (b1, bd) or NULL; y, sc planes with image
+ *   strides y_sn, sc_sn.  H, W <= 4095, Cin H W <= 2^28.
+ * ------------------------------------------------------------------------------------------ */
+int itermvs_down_conv(const float* x, int64_t x_sn, int32_t N, int32_t Cin, int32_t H, int32_t W, const void* w_packed,
+                      const float* bias, int32_t C, float* y, int64_t y_sn, float* sc, int64_t sc_sn, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * itermvs_lateral_conv3x3 -- one level of FeatureNet's top-down path in ONE launch (models/net.py:48-50; test mode :62-63):
  *     intra = F.interpolate(coarse, scale_factor=2, mode="bilinear") + inner(fine)       1x1 layer Cf -> 48, bias
  *     out   = output(intra)                                                               3x3 layer 48 -> Cout, bias, padding 1

@@ -197,7 +197,10 @@ class InferenceEngine:
         wt, bias, c = self.pk[key]
         n, _, hh, ww = x.shape
         sc = torch.empty((n, c, (hh - 1) // 2 + 1, (ww - 1) // 2 + 1), device=x.device)
-        y = ops.conv2d(x, wt, bias, stride=2, act="relu", split=(c, "none", sc))
+        if self.split3:         # bf16x3: one cooperative launch that stages each tile once for all 2c output channels
+            y, sc = ops.down_conv(x, wt, bias, c, out_b=sc)
+        else:
+            y = ops.conv2d(x, wt, bias, stride=2, act="relu", split=(c, "none", sc))
         return self._cbr(y, name + "conv2.", 1, "relu", add=sc)
 
     def feature_net(self, x: Tensor, compose=None, out: Tuple[Tensor, Tensor, Tensor, Tensor] = None) -> Dict[int, Tensor]:

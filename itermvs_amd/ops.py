@@ -1120,7 +1120,6 @@ def split_bf16x3(t: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
 #   True  -> bf16x3 split on v_mfma_f32_16x16x32_bf16 (conv_tile3.hip, weight_format 3): fp32-comparable error, 2.7x less matrix time
 #   False -> exact fp32 MFMA (conv_tile.hip, weight_format 2): bit-for-bit an fmaf chain
 MFMA_SPLIT3_DEFAULT = True
-SPLIT3_STRIDE2 = False      # True: stride-2 3x3 layers (Cin > 8) of a split3 MfmaWeight on the bf16 instruction as well (measured slower)
 
 
 class MfmaWeight:
@@ -1207,10 +1206,10 @@ def conv2d(x: Tensor, weight, bias=None, *, ksize: int = 3, stride: int = 1, pad
             raise RuntimeError("conv2d: MfmaWeight does not match the input channels / kernel size")
         cout = weights[0].cout
         tiled = transposed or all(_use_tile(wt, stride, dilation) for wt in weights)
-        # (stride-2 layers keep the fp32 form: in the step the split form measured 30.2 us per launch against 28.0 -- their halo tiles
-        #  leave no LDS for two resident workgroups and four channel blocks re-stage and re-split each tile; SPLIT3_STRIDE2 = True
-        #  selects the split form for them, profiles/r06/r06l_*)
-        split3 = (tiled and not transposed and (stride == 1 or (stride == 2 and cin > 8 and dilation == 1 and SPLIT3_STRIDE2))
+        # (stride-2 layers keep the fp32 form here: through this kernel every channel block re-stages and re-splits the halo tile, and
+        #  the split form measured 30.2 us per launch against 28.0, profiles/r06/r06l_*; FeatureNet's two stride-2 pairs run in bf16x3
+        #  through down_conv, which stages each tile once for all output channels)
+        split3 = (tiled and not transposed and stride == 1
                   and all(wt.tile3 is not None for wt in weights)
                   and (cin > 8 or dilation == 1))                    # (the tap-pair form of 5..8 channels: no dilation)
         weights = [(wt.tile3 if split3 else wt.tile) if tiled else wt.data for wt in weights]
@@ -1734,6 +1733,41 @@ def res_chain16(y1: Tensor, shortcut: Tensor, weights: Sequence["MfmaWeight"], b
         CONV_FLOP_COUNTER["flops"] += 3 * 2.0 * n * h * w * 16 * 16 * 9
         CONV_FLOP_COUNTER["launches"] += 1
     return out
+
+
+def down_conv(x: Tensor, packed: "MfmaWeight", bias: Optional[Tensor], split_channel: int, out: Optional[Tensor] = None,
+              out_b: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """itermvs_down_conv: a residual block's stride-2 pair in one launch -- y = relu(conv3x3_s2(x; W1) + b1) and
+    sc = conv3x3_s2(x; Wd) + bd (padding 1); ``x`` [N,Cin,H,W] planes, ``packed`` = MfmaWeight(cat(W1, Wd), split3=True),
+    ``bias`` = cat(b1, bd) or None, ``split_channel`` = C, the channels of each result; (Cin, C) = (16, 32) or (32, 48).
+    ``out`` / ``out_b``: destinations [N,C,(H-1)//2+1,(W-1)//2+1] (planes).  Returns (y, sc)."""
+    ptr, x_sn = _planes(x, "down_conv input")
+    n, cin, h, w = x.shape
+    c = int(split_channel)
+    if not isinstance(packed, MfmaWeight) or packed.ksize != 3 or packed.transposed or packed.cin != cin or packed.cout != 2 * c:
+        raise RuntimeError("down_conv: weight must be the 3x3 MfmaWeight of cat(W1, Wd) [2C,Cin,3,3]")
+    if packed.tile3 is None:
+        raise RuntimeError("down_conv: weight must be built with split3=True (bf16x3 form)")
+    if not packed.tile3.is_cuda or packed.tile3.dtype != torch.bfloat16:
+        raise RuntimeError("down_conv weights: expected bfloat16 ROCm tensors (MfmaWeight.tile3)")
+    ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    res = []
+    for t, name in ((out, "down_conv output"), (out_b, "down_conv shortcut output")):
+        if t is None:
+            t = torch.empty((n, c, ho, wo), device=x.device, dtype=torch.float32)
+        elif tuple(t.shape) != (n, c, ho, wo) or t.dtype != torch.float32:
+            raise RuntimeError(f"{name}: has shape {tuple(t.shape)}, expected float32 {(n, c, ho, wo)}")
+        res.append((t,) + _planes(t, name))
+    (y, py, y_sn), (sc, ps, s_sn) = res
+    bl = None if bias is None else _dev(bias, "down_conv bias").float().contiguous()
+    if bl is not None and bl.numel() != 2 * c:
+        raise RuntimeError(f"down_conv: bias has {bl.numel()} elements, expected {2 * c}")
+    check(_lib.load().itermvs_down_conv(ptr, x_sn, n, cin, h, w, packed.tile3.data_ptr(), _ptr(bl), c, py, y_sn, ps, s_sn, _stream()),
+          "itermvs_down_conv")
+    if CONV_FLOP_COUNTER["enabled"]:
+        CONV_FLOP_COUNTER["flops"] += 2.0 * n * ho * wo * 2 * c * cin * 9
+        CONV_FLOP_COUNTER["launches"] += 1
+    return y, sc
 
 
 def lateral_conv3x3(fine: Tensor, coarse: Tensor, w_lat: "MfmaWeight", b_lat: Optional[Tensor], w_out: "MfmaWeight",
