@@ -33,7 +33,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define ITERMVS_ABI_VERSION 18
+#define ITERMVS_ABI_VERSION 19
 #define ITERMVS_MAX_SRC 16     /* source views per reference view (pair.txt holds 10) */
 #define ITERMVS_MAX_HYP 8      /* hypotheses per level in the iteration branch (4,4,2) */
 #define ITERMVS_GROUPS 8       /* models/itermvs.py:28  */
@@ -566,6 +566,33 @@ typedef struct itermvs_conv_params {
 } itermvs_conv_params;
 
 int itermvs_conv2d(const itermvs_conv_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * itermvs_conv2d_plan -- diagnostic (ABI 19): WHICH kernel itermvs_conv2d runs for `p`.  Runs exactly the validation and the
+ * kernel choice of itermvs_conv2d and returns: same status for every rejected block, ITERMVS_OK and `*plan` otherwise.  It
+ * never reads through the data pointers (only whether they are set) and makes no device call, so it works on host memory and
+ * without a GPU.  Fields that do not apply to the back end are 0.
+ * ------------------------------------------------------------------------------------------ */
+typedef enum itermvs_conv_backend {
+    ITERMVS_CONV_DIRECT = 0,        /* conv_direct_kernel<CT, KS>                          weight_format 0 */
+    ITERMVS_CONV_MFMA = 1,          /* conv_mfma_kernel<MB, NB, KS>                        weight_format 1 */
+    ITERMVS_CONV_MFMA_SPLITK = 2,   /* conv_mfma_splitk_kernel<MB, KS> */
+    ITERMVS_CONV_LATERAL_UP2 = 3,   /* lateral_up2_kernel<MB> */
+    ITERMVS_CONV_TILE = 4,          /* conv_tile_kernel<MB, S, STRIDE, DIL, TH, TWT, CPS>  weight_format 2 */
+    ITERMVS_CONV_DECONV = 5,        /* deconv_tile_kernel<MB, S, TH, NCH> */
+    ITERMVS_CONV_TILE3 = 6,         /* conv_tile3_kernel<MB, STRIDE, DIL, TH, TWT, CPS>    weight_format 3 */
+    ITERMVS_CONV_TILE3_PAIR = 7     /* conv_tile3_kernel<MB, 1, 1, 8, 2, 1, 1, INCL> */
+} itermvs_conv_backend;
+
+typedef struct itermvs_conv_plan {
+    int32_t backend;                                   /* itermvs_conv_backend */
+    int32_t MB, NB, CT, KS, S, STRIDE, DIL, TH, TWT, CPS, NCH, PAIR, INCL;   /* template arguments of the kernel */
+    int32_t lds_bytes;                                 /* dynamic LDS of the launch */
+    int32_t tiles_x, tiles_y, ncb, nstage, total;      /* tile grid, channel blocks, stages per tile, N * tiles_y * tiles_x */
+    int32_t Hout, Wout;
+} itermvs_conv_plan;
+
+int itermvs_conv2d_plan(const itermvs_conv_params* p, itermvs_conv_plan* plan);
 
 /* ------------------------------------------------------------------------------------------
  * itermvs_corrnet -- the whole CorrNet (models/itermvs.py:352-381: conv0..conv2, the two transposed convolutions with

@@ -15,7 +15,7 @@ MAX_HYP = 8
 GROUPS = 8
 F32, F16, BF16 = 0, 1, 2      # itermvs_dtype: storage type of feature maps
 GT_DTU, GT_BLENDEDMVS = 0, 1  # itermvs_gt_pyramid recipes
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libitermvs_hip.so")
@@ -86,6 +86,17 @@ class ConvParams(C.Structure):
                 ("split_cout", C.c_int32), ("act_b", C.c_int32), ("in_layout", C.c_int32), ("out_b", C.c_void_p), ("out_b_sn", C.c_int64)]
 
 
+class ConvPlan(C.Structure):
+    """itermvs_conv_plan"""
+    BACKENDS = ("direct", "mfma", "mfma_splitk", "lateral_up2", "tile", "deconv", "tile3", "tile3_pair")
+    _fields_ = [(n, C.c_int32) for n in ("backend", "MB", "NB", "CT", "KS", "S", "STRIDE", "DIL", "TH", "TWT", "CPS", "NCH", "PAIR", "INCL",
+                                         "lds_bytes", "tiles_x", "tiles_y", "ncb", "nstage", "total", "Hout", "Wout")]
+
+    def __str__(self):
+        shown = [f"{n}={getattr(self, n)}" for n, _ in self._fields_[1:] if getattr(self, n)]
+        return f"{self.BACKENDS[self.backend]} " + " ".join(shown)
+
+
 # name -> (restype, argtypes); every symbol include/itermvs_hip.h declares
 PROTOTYPES = {
     "itermvs_version": (C.c_int, []),
@@ -144,6 +155,7 @@ PROTOTYPES = {
     "itermvs_bilinear_up": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                       C.c_void_p]),
     "itermvs_conv2d": (C.c_int, [C.POINTER(ConvParams), C.c_void_p]),
+    "itermvs_conv2d_plan": (C.c_int, [C.POINTER(ConvParams), C.POINTER(ConvPlan)]),
     "itermvs_corrnet": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
                                   C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "itermvs_corrnet_bf16x3": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,

@@ -22,23 +22,15 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "conv_plan.hpp"
 
 namespace itermvs {
 
-struct ConvArgs {
-    const float* in;
-    float* out;
-    float* out2;          // optional second copy of the result (contiguous [N,Cout,P])
-    const float* add;     // residual, added before the activation
-    const float* aux1;    // epilogue operand (h for the GRU forms)
-    const float* aux2;    // epilogue operand (z for the GRU update)
-    int64_t in_sn, out_sn, add_sn, aux1_sn, aux2_sn;
-    const float* weight[3];
-    const float* bias[3];
-    int seg_end[3];
-    int N, Cin, Hin, Win, Cout, Hout, Wout;
+struct ConvArgs : ConvArgsBase {
+    int Cin, Hin, Win, Cout, Hout, Wout;
     int stride, pad, dil, act;
 };
+static_assert(sizeof(ConvArgs) == 192, "kernel argument layout");
 
 __device__ __forceinline__ float epilogue(float v, int act, float add, float a1, float a2) {
     v += add;
@@ -106,102 +98,64 @@ __global__ void __launch_bounds__(256) conv_direct_kernel(const ConvArgs a) {
     }
 }
 
-template <int KS>
-static int launch_direct(const ConvArgs& a, int ct, hipStream_t stream) {
-    const int P = a.Hout * a.Wout;
-    const dim3 grid((P + 255) / 256, a.Cout / ct, a.N);
-    switch (ct) {
-        case 32: hipLaunchKernelGGL((conv_direct_kernel<32, KS>), grid, dim3(256), 0, stream, a); break;
-        case 16: hipLaunchKernelGGL((conv_direct_kernel<16, KS>), grid, dim3(256), 0, stream, a); break;
-        case 8: hipLaunchKernelGGL((conv_direct_kernel<8, KS>), grid, dim3(256), 0, stream, a); break;
-        case 4: hipLaunchKernelGGL((conv_direct_kernel<4, KS>), grid, dim3(256), 0, stream, a); break;
-        default: hipLaunchKernelGGL((conv_direct_kernel<1, KS>), grid, dim3(256), 0, stream, a); break;
-    }
-    return itermvs_launch_status();
-}
-
 }  // namespace itermvs
 
 using namespace itermvs;
 
-int itermvs_conv2d_mfma(const itermvs_conv_params* p, int hout, int wout, hipStream_t stream);      // conv_mfma.hip
-int itermvs_conv2d_tile(const itermvs_conv_params* p, int hout, int wout, hipStream_t stream);      // conv_tile.hip
-int itermvs_deconv2d_tile(const itermvs_conv_params* p, hipStream_t stream);                        // conv_tile.hip
-int itermvs_conv2d_tile3(const itermvs_conv_params* p, int hout, int wout, hipStream_t stream);     // conv_tile3.hip
+// the back ends: fill their argument block from the base + the plan and launch the instantiation the plan names
+using ConvBackend = int(const ConvArgsBase& base, const itermvs_conv_params* p, const itermvs_conv_plan& pl, int persist, hipStream_t stream);
+ConvBackend itermvs_conv2d_mfma, itermvs_conv2d_tile, itermvs_deconv2d_tile, itermvs_conv2d_tile3;   // conv_mfma.hip, conv_tile.hip (two), conv_tile3.hip
 
-static int conv2d_impl(const itermvs_conv_params* p, void* stream);
+static int conv2d_direct(const ConvArgsBase& base, const itermvs_conv_params* p, const itermvs_conv_plan& pl, int, hipStream_t stream) {
+    ConvArgs a;
+    fill_conv_args(a, base, p, pl);
+    a.stride = p->stride; a.dil = p->dilation;
+    const dim3 grid((pl.Hout * pl.Wout + 255) / 256, p->Cout / pl.CT, p->N);
+#define ITERMVS_DIRECT(CT_, KS_) \
+    if (pl.CT == CT_ && p->ksize == KS_) hipLaunchKernelGGL((conv_direct_kernel<CT_, KS_>), grid, dim3(256), 0, stream, a);
+    ITERMVS_DIRECT(32, 3) ITERMVS_DIRECT(16, 3) ITERMVS_DIRECT(8, 3) ITERMVS_DIRECT(4, 3) ITERMVS_DIRECT(1, 3)
+    ITERMVS_DIRECT(32, 1) ITERMVS_DIRECT(16, 1) ITERMVS_DIRECT(8, 1) ITERMVS_DIRECT(4, 1) ITERMVS_DIRECT(1, 1)
+#undef ITERMVS_DIRECT
+    return itermvs_launch_status();
+}
+
+// The tuning of this call: a constant in the product build (itermvs_tuning_env is nullptr there).  A `make TUNING=1` library reads
+// the switches once, except the two FORCE overrides, which tools/conv_bench.py --sweep / --sweep3 change between calls.
+static ConvTuning conv_tuning() {
+    static const ConvTuning fixed = [] {
+        ConvTuning t = kConvTuningDefault;
+        if (const char* e = itermvs_tuning_env("ITERMVS_TILE_PERSIST")) t.persist = atoi(e) < 1 ? 4 : atoi(e);
+        if (const char* e = itermvs_tuning_env("ITERMVS_TILE_TUNED")) t.tuned = e[0] != '0';
+        if (const char* e = itermvs_tuning_env("ITERMVS_TILE_MINWORK")) t.min_work = atoi(e);
+        if (const char* e = itermvs_tuning_env("ITERMVS_CONV_SPLITK")) t.splitk = e[0] != '0';
+        return t;
+    }();
+    ConvTuning t = fixed;
+    if (const char* e = itermvs_tuning_env("ITERMVS_TILE_FORCE")) t.tile_force = {e[0] - '0', e[2] - '0'};       // "shape,mb"
+    if (const char* e = itermvs_tuning_env("ITERMVS_TILE3_FORCE")) t.tile3_force = {e[0] - '0', e[2] - '0'};
+    return t;
+}
+
+extern "C" int itermvs_conv2d_plan(const itermvs_conv_params* p, itermvs_conv_plan* plan) {
+    ConvArgsBase base;
+    return conv_validate_plan(p, conv_tuning(), &base, plan);
+}
+
+// validate, plan, launch(plan)
+static int conv2d_impl(const itermvs_conv_params* p, hipStream_t stream) {
+    const ConvTuning t = conv_tuning();
+    ConvArgsBase base;
+    itermvs_conv_plan pl;
+    const int rc = conv_validate_plan(p, t, &base, &pl);
+    if (rc != ITERMVS_OK) return rc;
+    static ConvBackend* const backend[] = {conv2d_direct, itermvs_conv2d_mfma, itermvs_conv2d_mfma, itermvs_conv2d_mfma, itermvs_conv2d_tile,
+                                           itermvs_deconv2d_tile, itermvs_conv2d_tile3, itermvs_conv2d_tile3};      // by itermvs_conv_backend
+    return backend[pl.backend](base, p, pl, t.persist, stream);
+}
 
 extern "C" int itermvs_conv2d(const itermvs_conv_params* p, void* stream) {
     itermvs_profile_begin(3, (hipStream_t)stream);
-    const int rc = conv2d_impl(p, stream);
+    const int rc = conv2d_impl(p, (hipStream_t)stream);
     itermvs_profile_end(3, (hipStream_t)stream);
     return rc;
-}
-
-static int conv2d_impl(const itermvs_conv_params* p, void* stream) {
-    ITERMVS_RETURN_IF(!p, ITERMVS_ERR_NULL);
-    ITERMVS_RETURN_IF(!p->in || !p->out || !p->weight[0], ITERMVS_ERR_NULL);
-    ITERMVS_RETURN_IF(p->N < 1 || p->Cin < 1 || p->Cout < 1 || p->Hin < 1 || p->Win < 1, ITERMVS_ERR_DIMS);
-    ITERMVS_RETURN_IF(p->ksize != 1 && p->ksize != 3, ITERMVS_ERR_DIMS);
-    ITERMVS_RETURN_IF(p->n_seg < 1 || p->n_seg > 3 || p->act < 0 || p->act > 7, ITERMVS_ERR_DIMS);
-    ITERMVS_RETURN_IF((p->act == 6 || p->act == 7) && (!p->aux1 || p->add || p->out2 || p->out_layout != 0 || (p->Cout != 16 && p->Cout != 32) || (p->weight_format != 2 && p->weight_format != 3) || p->ksize != 3 ||
-                                      p->split_cout != 0 || p->transposed || p->n_seg != 1), ITERMVS_ERR_DIMS);
-    ITERMVS_RETURN_IF((p->act == 4 || p->act == 5 || p->act == 6 || p->act == 7) && !p->aux1, ITERMVS_ERR_NULL);
-    ITERMVS_RETURN_IF(p->act == 5 && !p->aux2, ITERMVS_ERR_NULL);
-    ITERMVS_RETURN_IF(p->act >= 2 && p->add, ITERMVS_ERR_DIMS);   // residual add only with none / relu
-    ITERMVS_RETURN_IF(p->add_mode < 0 || p->add_mode > 1, ITERMVS_ERR_DIMS);
-    ITERMVS_RETURN_IF(p->out_layout < 0 || p->out_layout > 3, ITERMVS_ERR_DIMS);
-    ITERMVS_RETURN_IF(p->in_layout != 0 && p->in_layout != 1, ITERMVS_ERR_LAYOUT);
-    // channels-last input: the 8-channel tap-pair form of the bf16x3 kernel only (conv_tile3.hip)
-    ITERMVS_RETURN_IF(p->in_layout == 1 && (p->weight_format != 3 || p->ksize != 3 || p->Cin != 8 || p->stride != 1 || p->dilation != 1 || p->transposed),
-                      ITERMVS_ERR_LAYOUT);
-    ITERMVS_RETURN_IF(p->in_layout == 1 && (((uintptr_t)p->in) % 16 || p->in_sn % 4), ITERMVS_ERR_ALIGN);
-    if (p->split_cout != 0) {
-        ITERMVS_RETURN_IF((p->weight_format != 2 && p->weight_format != 3) || p->transposed || p->out_layout != 0 || p->add || p->out2, ITERMVS_ERR_DIMS);
-        ITERMVS_RETURN_IF(p->split_cout < 16 || p->split_cout >= p->Cout || (p->split_cout & 15), ITERMVS_ERR_DIMS);
-        ITERMVS_RETURN_IF(!p->out_b || p->act_b < 0 || p->act_b > 4 || p->act > 4, ITERMVS_ERR_DIMS);
-        ITERMVS_RETURN_IF(p->act_b == 4 && !p->aux1, ITERMVS_ERR_NULL);
-    }
-    ITERMVS_RETURN_IF(p->out_layout >= 1 && (p->weight_format == 0 || p->transposed || p->act != 0 || p->add || (p->Cout & 3)),
-                      ITERMVS_ERR_DIMS);
-    ITERMVS_RETURN_IF(p->add_mode == 1 && (!p->add || p->weight_format == 0 || p->transposed || p->act != 0), ITERMVS_ERR_DIMS);
-    ConvArgs a;
-    a.in = p->in; a.out = p->out; a.out2 = p->out2; a.add = p->add; a.aux1 = p->aux1; a.aux2 = p->aux2;
-    a.in_sn = p->in_sn; a.out_sn = p->out_sn; a.add_sn = p->add_sn; a.aux1_sn = p->aux1_sn; a.aux2_sn = p->aux2_sn;
-    for (int i = 0; i < 3; ++i) {
-        const int k = i < p->n_seg ? i : p->n_seg - 1;
-        ITERMVS_RETURN_IF(!p->weight[k], ITERMVS_ERR_NULL);
-        a.weight[i] = p->weight[k];
-        a.bias[i] = p->bias[k];
-        a.seg_end[i] = i < p->n_seg - 1 ? p->seg_end[i] : p->N;
-    }
-    a.N = p->N; a.Cin = p->Cin; a.Hin = p->Hin; a.Win = p->Win; a.Cout = p->Cout;
-    a.stride = p->stride; a.pad = p->pad; a.dil = p->dilation; a.act = p->act;
-    // largest channel tile that divides Cout ...
-    int ct = 1;
-    for (int c : {32, 16, 8, 4})
-        if (p->Cout % c == 0) { ct = c; break; }
-    if (p->transposed && p->weight_format == 2) {
-        const int rc = itermvs_deconv2d_tile(p, (hipStream_t)stream);
-        return rc == 1 ? ITERMVS_ERR_DIMS : rc;
-    }
-    ITERMVS_RETURN_IF(p->transposed, ITERMVS_ERR_DIMS);   // transposed convolutions exist in weight_format 2 only
-    ITERMVS_RETURN_IF(p->stride < 1 || p->dilation < 1 || p->pad < 0, ITERMVS_ERR_DIMS);
-    const int span = (p->ksize - 1) * p->dilation + 1;
-    a.Hout = (p->Hin + 2 * p->pad - span) / p->stride + 1;
-    a.Wout = (p->Win + 2 * p->pad - span) / p->stride + 1;
-    ITERMVS_RETURN_IF(a.Hout < 1 || a.Wout < 1, ITERMVS_ERR_DIMS);
-    ITERMVS_RETURN_IF(p->add_mode == 1 && ((a.Hout | a.Wout) & 1), ITERMVS_ERR_DIMS);
-    if (p->weight_format == 2) {   // LDS-tiled 3x3 kernels; the packed layout fits no other kernel
-        const int rc = itermvs_conv2d_tile(p, a.Hout, a.Wout, (hipStream_t)stream);
-        return rc == 1 ? ITERMVS_ERR_DIMS : rc;
-    }
-    if (p->weight_format == 3) {   // bf16x3 split on the bf16 MFMA (3x3, more than 8 input channels)
-        const int rc = itermvs_conv2d_tile3(p, a.Hout, a.Wout, (hipStream_t)stream);
-        return rc == 1 ? ITERMVS_ERR_DIMS : rc;
-    }
-    if (p->weight_format == 1) return itermvs_conv2d_mfma(p, a.Hout, a.Wout, (hipStream_t)stream);
-    // ... that still leaves >= 1024 workgroups (the VALU kernel keeps all CT channels in one thread)
-    while (ct > 4 && (int64_t)((a.Hout * a.Wout + 255) / 256) * (p->Cout / ct) * p->N < 1024) ct /= 2;
-    return p->ksize == 3 ? launch_direct<3>(a, ct, (hipStream_t)stream) : launch_direct<1>(a, ct, (hipStream_t)stream);
 }

@@ -20,23 +20,16 @@
 
 #include "common.hpp"
 #include "conv_epilogue.hpp"
+#include "conv_plan.hpp"
 
 namespace itermvs {
 
-struct MfmaArgs {
-    const float* in;
-    float* out;
-    float* out2;
-    const float* add;
-    const float* aux1;
-    const float* aux2;
-    int64_t in_sn, out_sn, add_sn, aux1_sn, aux2_sn;
-    const float* weight[3];   // packed [k*k][CinPad][CoutPad]
-    const float* bias[3];
-    int seg_end[3];
-    int N, Cin, CinPad, Hin, Win, Cout, CoutPad, Hout, Wout;
+struct MfmaArgs : ConvArgsBase {
+    // weight[]: packed [k*k][CinPad][CoutPad]
+    int Cin, CinPad, Hin, Win, Cout, CoutPad, Hout, Wout;
     int ksize, stride, pad, dil, act, add_mode, out_nhwc;
 };
+static_assert(sizeof(MfmaArgs) == 216, "kernel argument layout");
 
 __device__ __forceinline__ EpilogueArgs make_epilogue(const MfmaArgs& a, int n, int P) {
     EpilogueArgs e;
@@ -162,7 +155,7 @@ __global__ void __launch_bounds__(256) conv_mfma_kernel(const MfmaArgs a) {
 // are batched (two memory round trips per tile).  The arithmetic and its order are those of the generic epilogue
 // (== bilinear_up_kernel): results are bit-identical.  Measured 49 -> 36 us (level 1), 17.9 -> 14 us (level 2).
 // ---------------------------------------------------------------------------------------------
-constexpr int kLatTH = 4, kLatTW = 64;                       // output tile (rows = waves)
+// output tile kLatTH x kLatTW = 4 x 64 (rows = waves): conv_plan.hpp
 constexpr int kLatPH = kLatTH / 2 + 2, kLatPW = kLatTW / 2 + 2;   // coarse patch 4 x 34
 constexpr int kLatRS = 37;                                   // LDS row stride; channel stride 4 * 37 = 148 floats: the two
 constexpr int kLatCS = kLatPH * kLatRS;                      // channel quads of a half-wave land 16 banks apart
@@ -412,67 +405,33 @@ __global__ void __launch_bounds__(256) conv_mfma_splitk_kernel(const MfmaArgs a)
 
 using namespace itermvs;
 
-// called from itermvs_conv2d (conv.hip) for the non-transposed convolutions when weight_format == 1
-int itermvs_conv2d_mfma(const itermvs_conv_params* p, int hout, int wout, hipStream_t stream) {
+// called from itermvs_conv2d (conv.hip) with a plan of back end ITERMVS_CONV_MFMA, _MFMA_SPLITK or _LATERAL_UP2
+int itermvs_conv2d_mfma(const ConvArgsBase& base, const itermvs_conv_params* p, const itermvs_conv_plan& pl, int, hipStream_t stream) {
     MfmaArgs a;
-    a.in = p->in; a.out = p->out; a.out2 = p->out2; a.add = p->add; a.aux1 = p->aux1; a.aux2 = p->aux2;
-    a.in_sn = p->in_sn; a.out_sn = p->out_sn; a.add_sn = p->add_sn; a.aux1_sn = p->aux1_sn; a.aux2_sn = p->aux2_sn;
-    for (int i = 0; i < 3; ++i) {
-        const int k = i < p->n_seg ? i : p->n_seg - 1;
-        a.weight[i] = p->weight[k];
-        a.bias[i] = p->bias[k];
-        a.seg_end[i] = i < p->n_seg - 1 ? p->seg_end[i] : p->N;
+    fill_conv_args(a, base, p, pl);
+    a.CinPad = (p->Cin + 3) / 4 * 4; a.CoutPad = (p->Cout + 15) / 16 * 16;
+    a.ksize = p->ksize; a.stride = p->stride; a.dil = p->dilation; a.add_mode = p->add_mode; a.out_nhwc = p->out_layout;
+    const int P = pl.Hout * pl.Wout, mt = a.CoutPad / 16;
+    const bool k3 = p->ksize == 3;
+    if (pl.backend == ITERMVS_CONV_LATERAL_UP2) {
+        hipLaunchKernelGGL((lateral_up2_kernel<3>), dim3(pl.tiles_x * pl.tiles_y, 1, p->N), dim3(256), 0, stream, a, pl.tiles_x);
+    } else if (pl.backend == ITERMVS_CONV_MFMA_SPLITK) {       // the four waves of a block share one 16-pixel tile
+        const dim3 grid((P + 15) / 16, mt / pl.MB, p->N);
+#define ITERMVS_SPLITK(MB_, KS_) \
+    if (pl.MB == MB_ && p->ksize == KS_) hipLaunchKernelGGL((conv_mfma_splitk_kernel<MB_, KS_>), grid, dim3(256), 0, stream, a);
+        ITERMVS_SPLITK(2, 3) ITERMVS_SPLITK(2, 1) ITERMVS_SPLITK(1, 3) ITERMVS_SPLITK(1, 1)
+#undef ITERMVS_SPLITK
+    } else {
+        const int px_per_block = 4 * 16 * pl.NB;
+        const dim3 grid((P + px_per_block - 1) / px_per_block, mt / pl.MB, p->N);
+#define ITERMVS_LAUNCH(MB_, NB_)                                                                       \
+    if (pl.MB == MB_ && pl.NB == NB_) {                                                                 \
+        if (k3) hipLaunchKernelGGL((conv_mfma_kernel<MB_, NB_, 3>), grid, dim3(256), 0, stream, a);     \
+        else hipLaunchKernelGGL((conv_mfma_kernel<MB_, NB_, 1>), grid, dim3(256), 0, stream, a);        \
     }
-    a.N = p->N; a.Cin = p->Cin; a.CinPad = (p->Cin + 3) / 4 * 4; a.Hin = p->Hin; a.Win = p->Win;
-    a.Cout = p->Cout; a.CoutPad = (p->Cout + 15) / 16 * 16; a.Hout = hout; a.Wout = wout;
-    a.ksize = p->ksize; a.stride = p->stride; a.pad = p->pad; a.dil = p->dilation; a.act = p->act;
-    a.add_mode = p->add_mode; a.out_nhwc = p->out_layout;
-    const int P = hout * wout;
-    const int mt = a.CoutPad / 16;
-    // FeatureNet's lateral layers: 1x1 + bias + x2 bilinear up-sampled residual with the coarse patch staged in LDS
-    if (p->ksize == 1 && p->add_mode == 1 && p->add && p->out_layout == 0 && !p->out2 && p->act == 0 && p->stride == 1 && p->pad == 0 &&
-        p->n_seg == 1 && mt == 3 && !p->split_cout) {
-        const int tiles_x = (wout + kLatTW - 1) / kLatTW, tiles_y = (hout + kLatTH - 1) / kLatTH;
-        hipLaunchKernelGGL((lateral_up2_kernel<3>), dim3(tiles_x * tiles_y, 1, p->N), dim3(256), 0, stream, a, tiles_x);
-        return itermvs_launch_status();
-    }
-    // largest register blocking (MB x NB tiles of 16 channels x 16 pixels per wave) that still yields
-    // >= 2048 waves (2 per SIMD): bigger tiles need fewer loads per MFMA, more waves hide latency
-    struct Cfg { int mb, nb; };
-    const Cfg cfgs[] = {{3, 4}, {2, 4}, {3, 2}, {2, 2}, {1, 4}, {1, 2}, {3, 1}, {2, 1}, {1, 1}};
-    Cfg pick = {1, 1};
-    int64_t best_waves = -1;
-    for (const Cfg& c : cfgs) {
-        if (mt % c.mb != 0) continue;
-        const int64_t waves = (int64_t)p->N * ((P + 16 * c.nb - 1) / (16 * c.nb)) * (mt / c.mb);
-        if (waves >= 2048) { pick = c; best_waves = waves; break; }
-        if (waves > best_waves) { pick = c; best_waves = waves; }   // otherwise: the most waves available
-    }
-    // too few tiles even at 16x16 and a k-loop long enough to split: four waves per tile (split-K)
-    static const bool no_splitk = [] { const char* e = itermvs_tuning_env("ITERMVS_CONV_SPLITK"); return e && e[0] == '0'; }();
-    const int ksteps = p->ksize * p->ksize * (a.CinPad / 4);
-    const int64_t tiles16 = (int64_t)p->N * ((P + 15) / 16) * mt;       // waves of the <1,1> configuration
-    if (!no_splitk && tiles16 < 8192 && ksteps >= 16) {
-        const int mb = (mt % 2 == 0 && tiles16 / 2 >= 2048) ? 2 : 1;
-        const dim3 grid((P + 15) / 16, mt / mb, p->N);
-        if (mb == 2) {
-            if (p->ksize == 3) hipLaunchKernelGGL((conv_mfma_splitk_kernel<2, 3>), grid, dim3(256), 0, stream, a);
-            else hipLaunchKernelGGL((conv_mfma_splitk_kernel<2, 1>), grid, dim3(256), 0, stream, a);
-        } else {
-            if (p->ksize == 3) hipLaunchKernelGGL((conv_mfma_splitk_kernel<1, 3>), grid, dim3(256), 0, stream, a);
-            else hipLaunchKernelGGL((conv_mfma_splitk_kernel<1, 1>), grid, dim3(256), 0, stream, a);
-        }
-        return itermvs_launch_status();
-    }
-    const int px_per_block = 4 * 16 * pick.nb;
-    const dim3 grid((P + px_per_block - 1) / px_per_block, mt / pick.mb, p->N);
-#define ITERMVS_LAUNCH(MB_, NB_)                                                                              \
-    if (pick.mb == MB_ && pick.nb == NB_) {                                                                    \
-        if (p->ksize == 3) hipLaunchKernelGGL((conv_mfma_kernel<MB_, NB_, 3>), grid, dim3(256), 0, stream, a); \
-        else hipLaunchKernelGGL((conv_mfma_kernel<MB_, NB_, 1>), grid, dim3(256), 0, stream, a);               \
-    }
-    ITERMVS_LAUNCH(3, 4) ITERMVS_LAUNCH(2, 4) ITERMVS_LAUNCH(3, 2) ITERMVS_LAUNCH(2, 2) ITERMVS_LAUNCH(1, 4)
-    ITERMVS_LAUNCH(1, 2) ITERMVS_LAUNCH(3, 1) ITERMVS_LAUNCH(2, 1) ITERMVS_LAUNCH(1, 1)
+        ITERMVS_LAUNCH(3, 4) ITERMVS_LAUNCH(2, 4) ITERMVS_LAUNCH(3, 2) ITERMVS_LAUNCH(2, 2) ITERMVS_LAUNCH(1, 4)
+        ITERMVS_LAUNCH(1, 2) ITERMVS_LAUNCH(3, 1) ITERMVS_LAUNCH(2, 1) ITERMVS_LAUNCH(1, 1)
 #undef ITERMVS_LAUNCH
+    }
     return itermvs_launch_status();
 }

@@ -32,8 +32,6 @@ namespace itermvs {
 
 using f32x2 = __attribute__((ext_vector_type(2))) float;
 
-
-
 // -DITERMVS_TILE_TRACE (tools/ubench/conv_tile_trace.hip): wave 0 of workgroup 0 stamps the phases of its tiles
 #ifdef ITERMVS_TILE_TRACE
 __device__ unsigned long long g_tile_trace[8 * 64];
@@ -341,73 +339,16 @@ __global__ void __launch_bounds__(256) conv_tile_kernel(const TileArgs a) {
     }
 }
 
-constexpr int kLdsBudget = 64 * 1024;    // per workgroup (default dynamic-LDS limit; two workgroups fit a CU)
-
-template <int MB, int S, int STRIDE, int DIL, int TH, int TWT, int CPS>
-static constexpr int tile_lds_bytes(int nchunk) {
-    return (CPS * 4 * TileGeom<S, STRIDE, DIL, TH, TWT>::PL + nchunk * 36 * 16 * MB * S) * 4;
-}
-
-template <int MB, int S, int STRIDE, int DIL, int TH, int TWT, int CPS>
-static int launch_tile(TileArgs& a, int mt, hipStream_t stream) {
-    constexpr int TW = 16 * TWT;
-    const int lds = tile_lds_bytes<MB, S, STRIDE, DIL, TH, TWT, CPS>(a.nchunk);
-    if (lds > kLdsBudget) return 1;
-    a.tiles_x = (a.Wout + TW - 1) / TW;
-    a.tiles_y = (a.Hout + TH - 1) / TH;
-    a.ncb = mt / MB;
-    a.nstage = (a.nchunk + CPS - 1) / CPS;
-    a.total = a.N * a.tiles_y * a.tiles_x;
-    a.rcp_tiles_x = (uint32_t)((1ull << 32) / (uint32_t)a.tiles_x + 1);   // (unused when the divisor is 1)
-    a.rcp_tiles_y = (uint32_t)((1ull << 32) / (uint32_t)a.tiles_y + 1);
-    // persistent grid: about ITERMVS_TILE_PERSIST (default 4; measured 630 / 645 / 650 / 648 depth-maps/s at
-    // 2 / 3 / 4 / 8, bounded by what fits a CU) workgroups per CU in total, each walking the
-    // tile list of its channel block (one tile each when there are fewer tiles than that); never more than
-    // are resident at once -- a persistent workgroup queued behind another would serialise its tile list
-    static const int want = [] { const char* e = itermvs_tuning_env("ITERMVS_TILE_PERSIST"); const int v = e ? atoi(e) : 4; return v < 1 ? 4 : v; }();
-    int fit = 1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, conv_tile_kernel<MB, S, STRIDE, DIL, TH, TWT, CPS>, 256, lds) != hipSuccess || fit < 1)
-        fit = 1;
-    int gx = 256 * (want < fit ? want : fit) / a.ncb;
-    if (gx > a.total) gx = a.total;
-    if (gx < 1) gx = 1;
-    if (gx >= 16) gx &= ~7;              // a multiple of 8 workgroup columns: the XCD-banded tile order needs it (85 -> 80 costs nothing)
-    a.banded = gx % 8 == 0 && a.total >= gx ? 1 : 0;
-    const dim3 grid(gx, a.ncb);
-    hipLaunchKernelGGL((conv_tile_kernel<MB, S, STRIDE, DIL, TH, TWT, CPS>), grid, dim3(256), lds, stream, a);
-    return 0;
-}
-
-// chunks per stage: all chunks of a 2..4-chunk layer at once when input stages + weights fit the LDS budget
-template <int MB, int S, int STRIDE, int DIL, int TH, int TWT>
-static int launch_cps(TileArgs& a, int mt, hipStream_t stream) {
-    if constexpr (S == 4) {
-        if (a.nchunk == 3 && tile_lds_bytes<MB, S, STRIDE, DIL, TH, TWT, 3>(3) <= kLdsBudget)
-            return launch_tile<MB, S, STRIDE, DIL, TH, TWT, 3>(a, mt, stream);
-        if ((a.nchunk == 2 || a.nchunk == 4) && tile_lds_bytes<MB, S, STRIDE, DIL, TH, TWT, 2>(a.nchunk) <= kLdsBudget)
-            return launch_tile<MB, S, STRIDE, DIL, TH, TWT, 2>(a, mt, stream);
-    }
-    return launch_tile<MB, S, STRIDE, DIL, TH, TWT, 1>(a, mt, stream);
-}
-
-// tile shapes: big = 8 x 32 pixels (4 segments per wave), mid = 4 x 32 (2), small = 4 x 16 (1)
-template <int MB, int S, int STRIDE, int DIL>
-static int launch_shape(TileArgs& a, int mt, int shape, hipStream_t stream) {
-    if (shape == 2) {
-        if constexpr (STRIDE == 1) return launch_cps<MB, S, STRIDE, DIL, 8, 2>(a, mt, stream);
-        else return launch_cps<MB, S, STRIDE, DIL, 4, 2>(a, mt, stream);   // stride 2: the 8x32 halo tile is too big
-    } else if (shape == 1) {
-        return launch_cps<MB, S, STRIDE, DIL, 4, 2>(a, mt, stream);
-    }
-    return launch_cps<MB, S, STRIDE, DIL, 4, 1>(a, mt, stream);
-}
-
-template <int S, int STRIDE, int DIL>
-static int launch_mb(TileArgs& a, int mt, int mb, int shape, hipStream_t stream) {
-    if (mb == 3) return launch_shape<3, S, STRIDE, DIL>(a, mt, shape, stream);
-    if (mb == 2) return launch_shape<2, S, STRIDE, DIL>(a, mt, shape, stream);
-    return launch_shape<1, S, STRIDE, DIL>(a, mt, shape, stream);
-}
+// the instantiations of the ladder (conv_tile.hpp) at S channels per k-slot
+template <int S>
+struct TileKernels {
+    template <int MB, int STRIDE, int DIL, int TH, int TWT, int CPS>
+    struct At {
+        static_assert(tile_lds_bytes(MB, S, STRIDE, DIL, TH, TWT, CPS, 1) == (CPS * 4 * TileGeom<S, STRIDE, DIL, TH, TWT>::PL + 36 * 16 * MB * S) * 4,
+                      "the plan's LDS size is the kernel's");
+        static int run(TileLaunch& t) { return launch_persistent(conv_tile_kernel<MB, S, STRIDE, DIL, TH, TWT, CPS>, t); }
+    };
+};
 
 // ---------------------------------------------------------------------------------------------
 // ConvTranspose2d(3, stride 2, pad 1, output_padding 1) on the matrix cores (CorrNet, itermvs.py:359-363).
@@ -525,159 +466,31 @@ __global__ void __launch_bounds__(256) deconv_tile_kernel(const TileArgs a) {
     conv_epilogue<MB, 4>(e, acc, m0, q, pix_off, oyv, oxv);
 }
 
-template <int MB, int S, int NCH>
-static int launch_deconv(TileArgs& a, int mt, hipStream_t stream) {
-    constexpr int TH = 4, IN_PX = (TH + 1) * 17;
-    constexpr int PL = (IN_PX * S + 63) / 64 * 64 + (S == 4 ? 0 : S == 2 ? 32 : 16);
-    constexpr int lds = (NCH * 4 * PL + NCH * 36 * 16 * MB * S) * 4;
-    static_assert(lds <= kLdsBudget, "deconv tile does not fit LDS");
-    a.tiles_x = (a.Win + 15) / 16;
-    a.tiles_y = (a.Hin + TH - 1) / TH;
-    const dim3 grid(a.N * a.tiles_y * a.tiles_x, mt / MB);
-    hipLaunchKernelGGL((deconv_tile_kernel<MB, S, TH, NCH>), grid, dim3(256), lds, stream, a);
-    return 0;
-}
-
 }  // namespace itermvs
 
 using namespace itermvs;
 
-// called from itermvs_conv2d (conv.hip) when weight_format == 2; returns 1 when the shape is not covered
-// (the caller reports ITERMVS_ERR_DIMS: format-2 weights cannot feed another kernel)
-int itermvs_conv2d_tile(const itermvs_conv_params* p, int hout, int wout, hipStream_t stream) {
-    if (p->ksize != 3) return 1;
-    const bool s1d1 = p->stride == 1 && p->dilation == 1, s2d1 = p->stride == 2 && p->dilation == 1;
-    const bool s1d2 = p->stride == 1 && p->dilation == 2;
-    if (!s1d1 && !s2d1 && !s1d2) return 1;
-    TileArgs a;
-    a.banded = 0;
-    a.in = p->in; a.out = p->out; a.out2 = p->out2; a.add = p->add; a.aux1 = p->aux1; a.aux2 = p->aux2;
-    a.in_sn = p->in_sn; a.out_sn = p->out_sn; a.add_sn = p->add_sn; a.aux1_sn = p->aux1_sn; a.aux2_sn = p->aux2_sn;
-    for (int i = 0; i < 3; ++i) {
-        const int k = i < p->n_seg ? i : p->n_seg - 1;
-        a.weight[i] = p->weight[k];
-        a.bias[i] = p->bias[k];
-        a.seg_end[i] = i < p->n_seg - 1 ? p->seg_end[i] : p->N;
-    }
-    a.N = p->N; a.Cin = p->Cin; a.Hin = p->Hin; a.Win = p->Win;
-    a.Cout = p->Cout; a.CoutPad = (p->Cout + 15) / 16 * 16; a.Hout = hout; a.Wout = wout;
-    a.pad = p->pad; a.act = p->act; a.add_mode = p->add_mode; a.out_nhwc = p->out_layout;
-    a.split = p->split_cout; a.act_b = p->act_b; a.out_b = p->out_b; a.out_b_sn = p->out_b_sn;
-    const int S = p->Cin <= 4 ? 1 : p->Cin <= 8 ? 2 : 4;
-    a.nchunk = (p->Cin + 4 * S - 1) / (4 * S);
-    const int mt = a.CoutPad / 16;
-    // largest tile / channel blocking that still gives every CU >= 4 workgroups; otherwise the most workgroups
-    auto blocks = [&](int shape, int mb) -> int64_t {
-        const int th = shape == 2 && p->stride == 1 ? 8 : 4, tw = shape == 0 ? 16 : 32;
-        return (int64_t)((hout + th - 1) / th) * ((wout + tw - 1) / tw) * (mt / mb) * p->N;   // work items
-    };
-    // LDS bytes of a candidate when ALL chunks of a tile are staged together (launch_cps picks that when it fits)
-    auto full_stage_fits = [&](int sh, int m) {
-        const int th = sh == 2 && p->stride == 1 ? 8 : 4, tw = sh == 0 ? 16 : 32;
-        const int in_px = ((th - 1) * p->stride + 2 * p->dilation + 1) * ((tw - 1) * p->stride + 2 * p->dilation + 1);
-        const int pl = (in_px * S + 63) / 64 * 64 + (S == 4 ? 0 : S == 2 ? 32 : 16);
-        const int cps = a.nchunk == 4 ? 2 : a.nchunk;
-        return (cps * 4 * pl + a.nchunk * 36 * 16 * m * S) * 4 <= kLdsBudget;
-    };
-    // (only for layers of a few hundred tiles, where the per-tile chain of barriers and weight copies is what
-    //  bounds the launch; large layers amortise it over big tiles)
-    const bool deep = a.nchunk >= 2 && a.nchunk <= 4 && blocks(2, 1) < 1024;
-    const char* force = itermvs_tuning_env("ITERMVS_TILE_FORCE");             // "shape,mb" (tools/conv_bench.py --sweep)
-    static const bool tuned = [] { const char* e = itermvs_tuning_env("ITERMVS_TILE_TUNED"); return !e || e[0] != '0'; }();
-    static const int min_work = [] { const char* e = itermvs_tuning_env("ITERMVS_TILE_MINWORK"); return e ? atoi(e) : 1024; }();   // work items wanted: 4 workgroups per CU
-    int shape = 0, mb = 1;
-    int64_t best = -1;
-    bool found = false;
-    // multi-chunk layers: prefer candidates that stage a whole tile at once (one barrier pair and one weight
-    // copy per tile instead of one per chunk)
-    for (int pass = deep ? 0 : 1; pass < 2 && !found; ++pass) {
-        best = -1;
-        for (int sh = 2; sh >= 0 && !found; --sh)
-            for (int m : {3, 2, 1}) {
-                if (mt % m != 0 || (p->split_cout && (p->split_cout / 16) % m != 0)) continue;
-                if (pass == 0 && !full_stage_fits(sh, m)) continue;
-                const int64_t b = blocks(sh, m);
-                if (b >= min_work) { shape = sh; mb = m; found = true; break; }
-                if (b > best) { best = b; shape = sh; mb = m; }
-            }
-        if (best >= 0) found = true;       // pass 0 found a full-stage candidate (the one with the most work items)
-    }
-    // 16+ input channels (S = 4): measured sweep over all (tile shape, channel blocking) pairs on the layers of
-    // the path (tools/conv_bench.py --sweep): the 8x32 tile never wins there.  An even number of channel blocks
-    // runs best as 4x16 tiles with two blocks per wave (the stride-2 stages, 32->32, 48->32, 32->64: -10..-25 %),
-    // an odd one as 4x32 tiles with one block (16->16, 48->48, 48->16); the dilated ConvGRU convolutions as 4x32.
-    if (tuned && S == 4 && !p->split_cout) {
-        if (p->dilation == 2) {
-            if (a.nchunk == 3) { shape = 1; mb = 1; }
-        } else if (mt % 2 == 0) {
-            shape = 0; mb = 2;
-        } else {
-            shape = 1; mb = 1;
-        }
-    } else if (tuned && S == 2 && p->stride == 2 && mt % 2 == 0 && (!p->split_cout || (p->split_cout / 16) % 2 == 0)) {
-        shape = 0; mb = 2;                                                            // 8 -> 16+16, stride 2
-    } else if (tuned && S == 4 && p->split_cout) {
-        if (p->dilation == 2) { shape = 1; mb = 1; }                                  // z / r gates
-        else if ((p->split_cout / 16) % 2 == 0 && mt % 2 == 0) { shape = 0; mb = 2; }  // stride-2 conv + shortcut
-    }
-    if (force) {
-        shape = force[0] - '0';
-        mb = force[2] - '0';
-        if (shape < 0 || shape > 2 || mb < 1 || mb > 3 || mt % mb != 0) return 1;
-    }
-    const bool dot = p->act == 6 || p->act == 7;     // the epilogue contracts over ALL output channels: one block per wave
-    if (dot) {
-        mb = mt;
-        if (mt == 2) shape = 0;                      // two blocks per wave run as 4x16 tiles
-    }
-    // the weights of the channel block must fit LDS next to at least one input stage: narrow the block
-    int rc = 1;
-    for (; rc == 1 && mb >= 1; --mb) {
-        if (dot && mb != mt) return 1;
-        if (mt % mb != 0 || (p->split_cout && (p->split_cout / 16) % mb != 0)) continue;
-        if (S == 1) {
-            if (!s1d1) return 1;
-            rc = launch_mb<1, 1, 1>(a, mt, mb, shape, stream);
-        } else if (S == 2) {
-            if (s1d1) rc = launch_mb<2, 1, 1>(a, mt, mb, shape, stream);
-            else if (s2d1) rc = launch_mb<2, 2, 1>(a, mt, mb, shape, stream);
-            else return 1;
-        } else {
-            if (s1d1) rc = launch_mb<4, 1, 1>(a, mt, mb, shape, stream);
-            else if (s2d1) rc = launch_mb<4, 2, 1>(a, mt, mb, shape, stream);
-            else rc = launch_mb<4, 1, 2>(a, mt, mb, shape, stream);
-        }
-    }
-    if (rc != 0) return 1;
-    return itermvs_launch_status();
+// called from itermvs_conv2d (conv.hip) with a plan of back end ITERMVS_CONV_TILE
+int itermvs_conv2d_tile(const ConvArgsBase& base, const itermvs_conv_params* p, const itermvs_conv_plan& pl, int persist, hipStream_t stream) {
+    TileLaunch t = {{}, pl, persist, stream};
+    fill_tile_args(t.a, base, p, pl, (p->Cin + 4 * pl.S - 1) / (4 * pl.S));
+    if (pl.S == 1) return launch_ladder<TileKernels<1>::At, 1, 1, true, false>(t);
+    if (pl.S == 2) return pl.STRIDE == 1 ? launch_ladder<TileKernels<2>::At, 1, 1, true, false>(t) : launch_ladder<TileKernels<2>::At, 2, 1, true, false>(t);
+    if (pl.DIL == 2) return launch_ladder<TileKernels<4>::At, 1, 2, true, true>(t);
+    return pl.STRIDE == 1 ? launch_ladder<TileKernels<4>::At, 1, 1, true, true>(t) : launch_ladder<TileKernels<4>::At, 2, 1, true, true>(t);
 }
 
-// transposed convolutions (weight_format 2 built from the ConvTranspose2d weight with in/out channels swapped);
-// returns 1 when the shape is not covered
-int itermvs_deconv2d_tile(const itermvs_conv_params* p, hipStream_t stream) {
-    if (p->ksize != 3 || p->stride != 2 || p->pad != 1 || p->act > 1 || p->Cin <= 4 || p->Cin > 32) return 1;
+// transposed convolutions (weight_format 2 built from the ConvTranspose2d weight with in/out channels swapped): ITERMVS_CONV_DECONV
+int itermvs_deconv2d_tile(const ConvArgsBase& base, const itermvs_conv_params* p, const itermvs_conv_plan& pl, int, hipStream_t stream) {
     TileArgs a;
-    a.banded = 0;
-    a.in = p->in; a.out = p->out; a.out2 = p->out2; a.add = p->add; a.aux1 = nullptr; a.aux2 = nullptr;
-    a.in_sn = p->in_sn; a.out_sn = p->out_sn; a.add_sn = p->add_sn; a.aux1_sn = 0; a.aux2_sn = 0;
-    for (int i = 0; i < 3; ++i) {
-        const int k = i < p->n_seg ? i : p->n_seg - 1;
-        a.weight[i] = p->weight[k];
-        a.bias[i] = p->bias[k];
-        a.seg_end[i] = i < p->n_seg - 1 ? p->seg_end[i] : p->N;
+    fill_tile_args(a, base, p, pl, pl.NCH);
+    // (the epilogue of this kernel is bias, `add`, relu: it reads neither the aux operands nor the split fields)
+#define ITERMVS_DECONV(MB_, S_, NCH_)                                                                                                    \
+    if (pl.MB == MB_ && pl.S == S_ && pl.NCH == NCH_) {                                                                                  \
+        static_assert(deconv_lds_bytes(MB_, S_, NCH_) <= kLdsBudget, "deconv tile does not fit LDS");                                    \
+        hipLaunchKernelGGL((deconv_tile_kernel<MB_, S_, 4, NCH_>), dim3(pl.total, pl.ncb), dim3(256), pl.lds_bytes, stream, a);         \
     }
-    a.N = p->N; a.Cin = p->Cin; a.Hin = p->Hin; a.Win = p->Win;
-    a.Cout = p->Cout; a.CoutPad = (p->Cout + 15) / 16 * 16; a.Hout = 2 * p->Hin; a.Wout = 2 * p->Win;
-    a.pad = 1; a.act = p->act; a.add_mode = 0; a.out_nhwc = 0;
-    a.split = 0; a.act_b = 0; a.out_b = nullptr; a.out_b_sn = 0;
-    const int S = p->Cin <= 8 ? 2 : 4;
-    a.nchunk = (p->Cin + 4 * S - 1) / (4 * S);
-    const int mt = a.CoutPad / 16;
-    if (mt > 2) return 1;
-    int rc = 1;
-    if (S == 2) rc = mt == 2 ? launch_deconv<2, 2, 1>(a, mt, stream) : launch_deconv<1, 2, 1>(a, mt, stream);
-    else if (a.nchunk == 1) rc = mt == 2 ? launch_deconv<2, 4, 1>(a, mt, stream) : launch_deconv<1, 4, 1>(a, mt, stream);
-    else rc = mt == 2 ? launch_deconv<2, 4, 2>(a, mt, stream) : launch_deconv<1, 4, 2>(a, mt, stream);
-    if (rc != 0) return 1;
+    ITERMVS_DECONV(1, 2, 1) ITERMVS_DECONV(2, 2, 1) ITERMVS_DECONV(1, 4, 1) ITERMVS_DECONV(2, 4, 1) ITERMVS_DECONV(1, 4, 2) ITERMVS_DECONV(2, 4, 2)
+#undef ITERMVS_DECONV
     return itermvs_launch_status();
 }

@@ -44,7 +44,6 @@
 
 namespace itermvs {
 
-
 template <int STRIDE, int DIL, int TH, int TWT>
 struct Tile3Geom {
     static constexpr int TW = 16 * TWT;
@@ -340,7 +339,6 @@ __global__ void __launch_bounds__(256) conv_tile3_kernel(const TileArgs a) {
     }
 }
 
-
 #ifndef ITERMVS_TILE3_SPEC
 #define ITERMVS_TILE3_SPEC 0
 #endif
@@ -348,182 +346,38 @@ __global__ void __launch_bounds__(256) conv_tile3_kernel(const TileArgs a) {
 #include "experiments/conv_tile3_producer_consumer.inc"
 #endif
 
-constexpr int kLds3Budget = 80 * 1024;     // per workgroup: two workgroups fit the CU's 160 KB
-
+// The instantiations of the ladder (conv_tile.hpp).  Kernels that may take more than 64 KB of LDS raise their dynamic-LDS limit
+// once, here where they are launched.
 template <int MB, int STRIDE, int DIL, int TH, int TWT, int CPS>
-static constexpr int tile3_lds_bytes(int nchunk, int taps = 9) {
-    return CPS * 6 * Tile3Geom<STRIDE, DIL, TH, TWT>::PLB + nchunk * taps * 3 * 16 * MB * 32;
-}
-
-// PAIR form: one instantiation per channel blocking (8 x 32 tiles, one chunk)
-template <int MB, int INCL = 0>
-static int launch_tile3_pair(TileArgs& a, int mt, hipStream_t stream) {
-    constexpr int TH = 8, TWT = 2, TW = 16 * TWT;
-    const int lds = tile3_lds_bytes<MB, 1, 1, TH, TWT, 1>(1, 5);
-    auto kern = conv_tile3_kernel<MB, 1, 1, TH, TWT, 1, 1, INCL>;
-    a.tiles_x = (a.Wout + TW - 1) / TW;
-    a.tiles_y = (a.Hout + TH - 1) / TH;
-    a.ncb = mt / MB;
-    a.nstage = 1;
-    a.total = a.N * a.tiles_y * a.tiles_x;
-    a.rcp_tiles_x = (uint32_t)((1ull << 32) / (uint32_t)a.tiles_x + 1);
-    a.rcp_tiles_y = (uint32_t)((1ull << 32) / (uint32_t)a.tiles_y + 1);
-    int fit = 1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, kern, 256, lds) != hipSuccess || fit < 1) fit = 1;
-    int gx = itermvs_num_cus() * (4 < fit ? 4 : fit) / a.ncb;
-    if (gx > a.total) gx = a.total;
-    if (gx < 1) gx = 1;
-    if (gx >= 16) gx &= ~7;              // a multiple of 8 workgroup columns: the XCD-banded tile order needs it (85 -> 80 costs nothing)
-    a.banded = gx % 8 == 0 && a.total >= gx ? 1 : 0;
-    hipLaunchKernelGGL(kern, dim3(gx, a.ncb), dim3(256), lds, stream, a);
-    return 0;
-}
-
-template <int MB, int STRIDE, int DIL, int TH, int TWT, int CPS>
-static int launch_tile3(TileArgs& a, int mt, hipStream_t stream) {
-    constexpr int TW = 16 * TWT;
-    const int lds = tile3_lds_bytes<MB, STRIDE, DIL, TH, TWT, CPS>(a.nchunk);
-    if (lds > kLds3Budget) return 1;
-    auto kern = conv_tile3_kernel<MB, STRIDE, DIL, TH, TWT, CPS>;
-    static const bool big_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kLds3Budget) == hipSuccess;
-    if (lds > 64 * 1024 && !big_ok) return 1;
-    a.tiles_x = (a.Wout + TW - 1) / TW;
-    a.tiles_y = (a.Hout + TH - 1) / TH;
-    a.ncb = mt / MB;
-    a.nstage = (a.nchunk + CPS - 1) / CPS;
-    a.total = a.N * a.tiles_y * a.tiles_x;
-    a.rcp_tiles_x = (uint32_t)((1ull << 32) / (uint32_t)a.tiles_x + 1);
-    a.rcp_tiles_y = (uint32_t)((1ull << 32) / (uint32_t)a.tiles_y + 1);
-    static const int want = [] { const char* e = itermvs_tuning_env("ITERMVS_TILE_PERSIST"); const int v = e ? atoi(e) : 4; return v < 1 ? 4 : v; }();
-    int fit = 1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, kern, 256, lds) != hipSuccess || fit < 1) fit = 1;
-    int gx = itermvs_num_cus() * (want < fit ? want : fit) / a.ncb;
-    if (gx > a.total) gx = a.total;
-    if (gx < 1) gx = 1;
-    if (gx >= 16) gx &= ~7;              // a multiple of 8 workgroup columns: the XCD-banded tile order needs it (85 -> 80 costs nothing)
-    a.banded = gx % 8 == 0 && a.total >= gx ? 1 : 0;
-    hipLaunchKernelGGL(kern, dim3(gx, a.ncb), dim3(256), lds, stream, a);
-    return 0;
-}
-
-// chunks per stage: all chunks of a 2..4-chunk layer at once when the stages + weights fit the LDS budget
-template <int MB, int STRIDE, int DIL, int TH, int TWT>
-static int launch_cps3(TileArgs& a, int mt, hipStream_t stream) {
-#if ITERMVS_TILE3_SPEC
-    if (a.nchunk == 3 && tile3s_lds_bytes<MB, STRIDE, DIL, TH, TWT, 3>(3) <= kLds3sBudget)
-        return launch_tile3s<MB, STRIDE, DIL, TH, TWT, 3>(a, mt, stream);
-    if ((a.nchunk == 2 || a.nchunk == 4) && tile3s_lds_bytes<MB, STRIDE, DIL, TH, TWT, 2>(a.nchunk) <= kLds3sBudget)
-        return launch_tile3s<MB, STRIDE, DIL, TH, TWT, 2>(a, mt, stream);
-    return launch_tile3s<MB, STRIDE, DIL, TH, TWT, 1>(a, mt, stream);
+struct Tile3Kernels {
+    static_assert(tile3_lds_bytes(MB, STRIDE, DIL, TH, TWT, CPS, 1) == CPS * 6 * Tile3Geom<STRIDE, DIL, TH, TWT>::PLB + 27 * 16 * MB * 32,
+                  "the plan's LDS size is the kernel's");
+    static int run(TileLaunch& t) {
+#if ITERMVS_TILE3_SPEC       // A/B builds: the producer / consumer form, at the chunks per stage the plan chose for the kernel below
+        return launch_tile3s<MB, STRIDE, DIL, TH, TWT, CPS>(t.a, t.a.ncb * MB, t.stream) == 0 ? itermvs_launch_status() : ITERMVS_ERR_LAUNCH;
+#else
+        auto kern = conv_tile3_kernel<MB, STRIDE, DIL, TH, TWT, CPS>;
+        static const bool big_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kLds3Budget) == hipSuccess;
+        if (t.pl.lds_bytes > 64 * 1024 && !big_ok) return ITERMVS_ERR_LAUNCH;
+        return launch_persistent(kern, t);
 #endif
-    if (a.nchunk == 3 && tile3_lds_bytes<MB, STRIDE, DIL, TH, TWT, 3>(3) <= kLds3Budget)
-        return launch_tile3<MB, STRIDE, DIL, TH, TWT, 3>(a, mt, stream);
-    if ((a.nchunk == 2 || a.nchunk == 4) && tile3_lds_bytes<MB, STRIDE, DIL, TH, TWT, 2>(a.nchunk) <= kLds3Budget)
-        return launch_tile3<MB, STRIDE, DIL, TH, TWT, 2>(a, mt, stream);
-    return launch_tile3<MB, STRIDE, DIL, TH, TWT, 1>(a, mt, stream);
-}
-
-// tile shapes: 2 = 8 x 32 pixels (4 segments per wave; stride 1 only), 1 = 4 x 32 (2), 0 = 4 x 16 (1)
-template <int MB, int STRIDE, int DIL>
-static int launch_shape3(TileArgs& a, int mt, int shape, hipStream_t stream) {
-    if (shape == 2) {
-        if constexpr (STRIDE == 1 && MB < 3) return launch_cps3<MB, STRIDE, DIL, 8, 2>(a, mt, stream);
-        else return launch_cps3<MB, STRIDE, DIL, 4, 2>(a, mt, stream);
-    } else if (shape == 1) {
-        return launch_cps3<MB, STRIDE, DIL, 4, 2>(a, mt, stream);
     }
-    return launch_cps3<MB, STRIDE, DIL, 4, 1>(a, mt, stream);
-}
-
-template <int STRIDE, int DIL>
-static int launch_mb3(TileArgs& a, int mt, int mb, int shape, hipStream_t stream) {
-    if (mb == 3) return launch_shape3<3, STRIDE, DIL>(a, mt, shape, stream);
-    if (mb == 2) return launch_shape3<2, STRIDE, DIL>(a, mt, shape, stream);
-    return launch_shape3<1, STRIDE, DIL>(a, mt, shape, stream);
-}
+};
 
 }  // namespace itermvs
 
 using namespace itermvs;
 
-// called from itermvs_conv2d (conv.hip) when weight_format == 3; returns 1 when the shape is not covered
-int itermvs_conv2d_tile3(const itermvs_conv_params* p, int hout, int wout, hipStream_t stream) {
-    if (p->ksize != 3 || p->Cin <= 4) return 1;
-    if (p->in_layout == 1 && !(p->Cin == 8 && p->stride == 1 && p->dilation == 1)) return 1;      // channels-last input: the tap-pair form only
-    if (p->Cin <= 8 && !(p->stride == 1 && p->dilation == 1)) return 1;      // the tap-pair form: stride 1, no dilation
-    const bool s1d1 = p->stride == 1 && p->dilation == 1, s2d1 = p->stride == 2 && p->dilation == 1;
-    const bool s1d2 = p->stride == 1 && p->dilation == 2;
-    if (!s1d1 && !s2d1 && !s1d2) return 1;
-    TileArgs a;
-    a.banded = 0;
-    a.in = p->in; a.out = p->out; a.out2 = p->out2; a.add = p->add; a.aux1 = p->aux1; a.aux2 = p->aux2;
-    a.in_sn = p->in_sn; a.out_sn = p->out_sn; a.add_sn = p->add_sn; a.aux1_sn = p->aux1_sn; a.aux2_sn = p->aux2_sn;
-    for (int i = 0; i < 3; ++i) {
-        const int k = i < p->n_seg ? i : p->n_seg - 1;
-        a.weight[i] = p->weight[k];
-        a.bias[i] = p->bias[k];
-        a.seg_end[i] = i < p->n_seg - 1 ? p->seg_end[i] : p->N;
+// called from itermvs_conv2d (conv.hip) with a plan of back end ITERMVS_CONV_TILE3 or ITERMVS_CONV_TILE3_PAIR
+int itermvs_conv2d_tile3(const ConvArgsBase& base, const itermvs_conv_params* p, const itermvs_conv_plan& pl, int persist, hipStream_t stream) {
+    TileLaunch t = {{}, pl, pl.PAIR ? kPairPersist : persist, stream};
+    fill_tile_args(t.a, base, p, pl, (p->Cin + 15) / 16);
+    if (pl.PAIR) {            // one instantiation per (channel blocking, input layout): 8 x 32 tiles, one chunk
+#define ITERMVS_PAIR(MB_, INCL_) \
+    if (pl.MB == MB_ && pl.INCL == INCL_) return launch_persistent(conv_tile3_kernel<MB_, 1, 1, 8, 2, 1, 1, INCL_>, t);
+        ITERMVS_PAIR(1, 0) ITERMVS_PAIR(2, 0) ITERMVS_PAIR(1, 1) ITERMVS_PAIR(2, 1)
+#undef ITERMVS_PAIR
     }
-    a.N = p->N; a.Cin = p->Cin; a.Hin = p->Hin; a.Win = p->Win;
-    a.Cout = p->Cout; a.CoutPad = (p->Cout + 15) / 16 * 16; a.Hout = hout; a.Wout = wout;
-    a.pad = p->pad; a.act = p->act; a.add_mode = p->add_mode; a.out_nhwc = p->out_layout;
-    a.split = p->split_cout; a.act_b = p->act_b; a.out_b = p->out_b; a.out_b_sn = p->out_b_sn;
-    a.nchunk = (p->Cin + 15) / 16;
-    const int mt = a.CoutPad / 16;
-    const int split_blocks = p->split_cout ? p->split_cout / 16 : 0;
-    auto mb_ok = [&](int m) { return mt % m == 0 && (!split_blocks || split_blocks % m == 0); };
-    // Measured sweep over all (tile shape, channel blocking) pairs on the layers of the path (tools/conv_bench.py --sweep3,
-    // profiles/r05/r05e_conv_tile3_sweep.txt).  A wave wants MB * NB >= 4 accumulator tiles (operand reads per MFMA, see the
-    // header) but the split weights of a wide channel block crowd the LDS (48 -> 48 at MB = 3: 124 KB), and every channel
-    // block of a tile stages and splits the tile again:
-    //   dilated layers (ConvGRU, heads: 20 480 pixels, few tiles)      4x32 tiles, one block per wave
-    //   48 input channels (three chunks)                               8x32 tiles, one block
-    //   16 output channels                                             8x32 tiles
-    //   32 output channels                                             4x16 tiles, two blocks per wave
-    //   64+ output channels                                            4x16 tiles, one block
-    int shape = 1, mb = 1;
-    if (p->dilation == 2) { shape = 1; mb = 1; }
-    else if (a.nchunk >= 3 || mt == 1) { shape = p->stride == 1 ? 2 : 1; mb = 1; }
-    else if (mt == 2 && mb_ok(2)) { shape = 0; mb = 2; }
-    else { shape = 0; mb = 1; }
-    if (p->Cin <= 8) {            // PAIR form (weights packed as five tap pairs: ops.MfmaWeight)
-        if (p->split_cout) return 1;
-        const bool dotp = p->act == 6 || p->act == 7;
-        int rcp = 1;
-        if (p->in_layout == 1) {            // channels-last input: exactly 8 channels, 16-byte aligned pixels (checked in itermvs_conv2d)
-            if (mt == 1) rcp = launch_tile3_pair<1, 1>(a, mt, stream);
-            else if (mt == 2 && dotp) rcp = launch_tile3_pair<2, 1>(a, mt, stream);
-            else if (!dotp) rcp = launch_tile3_pair<1, 1>(a, mt, stream);
-        } else if (mt == 1) rcp = launch_tile3_pair<1>(a, mt, stream);
-        else if (mt == 2 && dotp) rcp = launch_tile3_pair<2>(a, mt, stream);
-        else if (!dotp) rcp = launch_tile3_pair<1>(a, mt, stream);
-        if (rcp != 0) return 1;
-        return itermvs_launch_status();
-    }
-    const char* force = itermvs_tuning_env("ITERMVS_TILE3_FORCE");            // "shape,mb" (tools/conv_bench.py --sweep3)
-    if (force) {
-        shape = force[0] - '0';
-        mb = force[2] - '0';
-        if (shape < 0 || shape > 2 || mb < 1 || mb > 3 || !mb_ok(mb)) return 1;
-    }
-    const bool dot = p->act == 6 || p->act == 7;     // the epilogue contracts over ALL output channels: one block per wave
-    if (dot) {
-        mb = mt;
-        if (mb > 3) return 1;
-    }
-    // the preferred (shape, channel blocking) first; when its stage + weights exceed the LDS budget (stride-2 halos, many
-    // input channels): smaller tiles, then narrower channel blocks
-    int rc = 1;
-    for (; rc == 1 && mb >= 1; --mb) {
-        if (dot && mb != mt) return 1;
-        if (!mb_ok(mb)) continue;
-        for (int sh = shape; rc == 1 && sh >= 0; --sh) {
-            if (s1d1) rc = launch_mb3<1, 1>(a, mt, mb, sh, stream);
-            else if (s2d1) rc = launch_mb3<2, 1>(a, mt, mb, sh, stream);
-            else rc = launch_mb3<1, 2>(a, mt, mb, sh, stream);
-            if (force) break;
-        }
-    }
-    if (rc != 0) return 1;
-    return itermvs_launch_status();
+    if (pl.DIL == 2) return launch_ladder<Tile3Kernels, 1, 2, false, true>(t);
+    return pl.STRIDE == 1 ? launch_ladder<Tile3Kernels, 1, 1, false, true>(t) : launch_ladder<Tile3Kernels, 2, 1, false, true>(t);
 }

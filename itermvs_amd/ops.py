@@ -1187,14 +1187,15 @@ def conv2d(x: Tensor, weight, bias=None, *, ksize: int = 3, stride: int = 1, pad
            act: str = "none", add: Optional[Tensor] = None, aux1: Optional[Tensor] = None,
            aux2: Optional[Tensor] = None, out: Optional[Tensor] = None, out2: Optional[Tensor] = None,
            transposed: bool = False, seg_end: Sequence[int] = (), add_up2: bool = False,
-           channels_last_out: bool = False, split=None) -> Tensor:
+           channels_last_out: bool = False, split=None, plan=None) -> Tensor:
     """itermvs_conv2d.  ``weight`` / ``bias``: packed tensor(s) (see pack_conv_weight); pass lists of up to
     three for per-segment weight sets with ``seg_end`` = batch boundaries.  ``add_up2``: ``add`` is the
     half-resolution tensor whose x2 bilinear up-sampling is added (fused F.interpolate).
     ``channels_last_out``: ``out`` is written in channels-last memory format ([N,H,W,C] dense, what the
     correlation kernels read); ``out2`` can still take the planar copy.
     ``split`` = (channel, act_b, out_b): output channels from ``channel`` on are a second result with its own
-    activation and destination (two convolutions of one input in one launch).  Returns ``out``."""
+    activation and destination (two convolutions of one input in one launch).  ``plan`` (a ``_lib.ConvPlan``) receives
+    itermvs_conv2d_plan's answer for this call: which kernel runs it.  Returns ``out``."""
     weights = list(weight) if isinstance(weight, (list, tuple)) else [weight]
     biases = list(bias) if isinstance(bias, (list, tuple)) else [bias] * len(weights)
     n, cin, hin, win = x.shape
@@ -1293,6 +1294,8 @@ def conv2d(x: Tensor, weight, bias=None, *, ksize: int = 3, stride: int = 1, pad
     if CONV_FLOP_COUNTER["enabled"]:
         CONV_FLOP_COUNTER["flops"] += 2.0 * n * hout * wout * cout_total * cin * ksize * ksize / (4.0 if transposed else 1.0)
         CONV_FLOP_COUNTER["launches"] += 1
+    if plan is not None:
+        check(_lib.load().itermvs_conv2d_plan(C.byref(p), C.byref(plan)), "itermvs_conv2d_plan")
     check(_lib.load().itermvs_conv2d(C.byref(p), _stream()), "itermvs_conv2d")
     return out
 

@@ -127,6 +127,56 @@ def test_conv_matches_torch(case, act, fmt):
     assert rel_err(got, want) <= 2e-6
 
 
+# name, back end per conv_arithmetic (bf16x3, fp32), cin, cout, what
+PLANNED = [
+    ("direct", ("direct", "direct"), 3, 8, dict(fmt="valu")),
+    ("pair", ("tile3_pair", "tile"), 8, 16, dict()),
+    ("tile3", ("tile3", "tile"), 16, 16, dict()),
+    ("dilated split", ("tile3", "tile"), 43, 64, dict(dil=2, split=32)),
+    ("deconv", ("deconv", "deconv"), 32, 16, dict(transposed=True)),
+    ("lateral", ("lateral_up2", "lateral_up2"), 16, 48, dict(k=1, up2=True)),
+]
+
+
+@pytest.mark.parametrize("layer", PLANNED, ids=[c[0] for c in PLANNED])
+def test_each_back_end_gets_its_argument_block(layer, conv_arithmetic):
+    """one small layer per back end of itermvs_conv2d at shapes with partial tiles (1 x C x 19 x 37; 2 x C x 20 x 36 where the
+    layer needs even sizes) against fp64 F.conv2d, and itermvs_conv2d_plan names the back end the case was written for"""
+    from itermvs_amd import _lib
+    name, backends, cin, cout, o = layer
+    k, dil, up2, tr = o.get("k", 3), o.get("dil", 1), o.get("up2", False), o.get("transposed", False)
+    n, h, w = (2, 20, 36) if up2 else (1, 19, 37)
+    gen = torch.Generator().manual_seed(cin * 7 + cout)
+    x = torch.randn((n, cin, h, w), generator=gen)
+    wt = torch.randn((cin, cout, k, k) if tr else (cout, cin, k, k), generator=gen) / (cin * k * k) ** 0.5
+    b = torch.randn((cout,), generator=gen)
+    pad = dil * (k // 2)
+    if tr:
+        want = F.conv_transpose2d(x.double(), wt.double(), b.double(), stride=2, padding=1, output_padding=1)
+    else:
+        want = F.conv2d(x.double(), wt.double(), b.double(), padding=pad, dilation=dil)
+    kw, tol = dict(ksize=k, pad=pad, dilation=dil), 2e-6
+    if up2:
+        coarse = torch.randn((n, cout, h // 2, w // 2), generator=gen)
+        want = want + F.interpolate(coarse.double(), scale_factor=2, mode="bilinear")
+        kw.update(add=coarse.to(DEV), add_up2=True)
+    if tr:
+        kw.update(transposed=True, stride=2, pad=1)
+    second = None
+    if "split" in o:                      # both halves through a sigmoid: the value range the error is measured against is compressed
+        want, tol = torch.sigmoid(want), 2e-5
+        second = torch.empty((n, cout - o["split"], h, w), device=DEV)
+        kw.update(act="sigmoid", split=(o["split"], "sigmoid", second))
+    pk = ops().pack_conv_weight(wt.to(DEV)) if o.get("fmt") == "valu" else ops().MfmaWeight(wt.to(DEV), transposed=tr)
+    plan = _lib.ConvPlan()
+    got = ops().conv2d(x.to(DEV), pk, b.to(DEV), plan=plan, **kw)
+    assert _lib.ConvPlan.BACKENDS[plan.backend] == backends[conv_arithmetic == "fp32"], str(plan)
+    if second is not None:
+        got = torch.cat([got, second], 1)
+    assert got.shape == want.shape
+    assert rel_err(got.double().cpu(), want) <= tol
+
+
 def test_transposed_conv_with_skip_and_segments():
     """CorrNet conv3/conv4 (itermvs.py:359-363) incl. the per-level weight sets of one launch (matrix-core format; the VALU
     format has no transposed form: the host refuses it)."""

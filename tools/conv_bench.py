@@ -3,7 +3,8 @@
 
 Every layer is captured into a hipGraph of REPS launches and the replay is timed, so the figure is the
 kernel time plus the ~4.5 us launch floor of a graph kernel node (no Python launch overhead).
-  conv_bench.py [filter]            default dispatch
+  conv_bench.py [filter]            default dispatch; under each layer its plan (itermvs_conv2d_plan: back end, template arguments,
+                                    LDS bytes, tile counts)
   conv_bench.py --sweep [filter]    every (tile shape, channel blocking) of the tiled kernel via ITERMVS_TILE_FORCE
 The sweep and the other overrides (ITERMVS_TILE_PERSIST, ITERMVS_TILE_MINWORK, ITERMVS_STEM_TH ...) exist only in a library
 built with `make -C itermvs_amd/csrc clean all TUNING=1`; the product build has no environment switches."""
@@ -46,14 +47,14 @@ LAYERS = [
 REPS = 20
 
 
-def time_layer(x, wt, k, stride, dil):
+def time_layer(x, wt, k, stride, dil, plan=None):
     pad = dil * (k // 2)
-    run = lambda: ops.conv2d(x, wt, None, ksize=k, stride=stride, pad=pad, dilation=dil, act="relu")
+    run = lambda plan=None: ops.conv2d(x, wt, None, ksize=k, stride=stride, pad=pad, dilation=dil, act="relu", plan=plan)
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(s):
         try:
-            out = run()
+            out = run(plan)
         except RuntimeError:
             return None, None
         run()
@@ -94,7 +95,8 @@ def main():
         x = torch.randn((n, cin, h, w), generator=gen).to(dev)
         wt = ops.MfmaWeight((torch.randn((cout, cin, k, k), generator=gen) / (cin * k * k) ** 0.5).to(dev))
         os.environ.pop("ITERMVS_TILE_FORCE", None)
-        us, out = time_layer(x, wt, k, stride, dil)
+        plan = _lib.ConvPlan()
+        us, out = time_layer(x, wt, k, stride, dil, plan)
         if us is None:
             print(f"{name:22s} not covered by this build / form", flush=True)
             continue
@@ -124,6 +126,7 @@ def main():
             res.sort()
             line += " | " + " ".join(f"s{sh}m{mb}:{t:.1f}" for t, sh, mb in res)
         print(line, flush=True)
+        print(f"{'':22s} plan: {plan}", flush=True)          # itermvs_conv2d_plan: the kernel of the default dispatch
     print(f"weighted total per depth map: {total:.0f} us")
 
 

@@ -11,9 +11,11 @@ void itermvs_profile_begin(int, hipStream_t) {}
 void itermvs_profile_end(int, hipStream_t) {}
 
 int main(int argc, char** argv) {
+    using namespace itermvs;
     const int cin = argc > 1 ? atoi(argv[1]) : 16, cout = argc > 2 ? atoi(argv[2]) : 16;
     const int H = argc > 3 ? atoi(argv[3]) : 256, W = argc > 4 ? atoi(argv[4]) : 320, N = argc > 5 ? atoi(argv[5]) : 5;
-    if (argc > 6) setenv("ITERMVS_TILE_PERSIST", argv[6], 1);
+    ConvTuning tuning = kConvTuningDefault;
+    if (argc > 6) tuning.persist = atoi(argv[6]) < 1 ? 4 : atoi(argv[6]);
     const int dil = argc > 7 ? atoi(argv[7]) : 1;
     const int S = cin <= 4 ? 1 : cin <= 8 ? 2 : 4, nch = (cin + 4 * S - 1) / (4 * S), coutp = (cout + 15) / 16 * 16;
     float *in, *out, *wt;
@@ -26,11 +28,17 @@ int main(int argc, char** argv) {
     p.in = in; p.out = out; p.in_sn = (int64_t)cin * H * W; p.out_sn = (int64_t)cout * H * W;
     p.weight[0] = wt; p.n_seg = 1; p.N = N; p.Cin = cin; p.Hin = H; p.Win = W; p.Cout = cout;
     p.ksize = 3; p.stride = 1; p.pad = dil; p.dilation = dil; p.act = 1; p.weight_format = 2;
+    ConvArgsBase base;
+    itermvs_conv_plan pl;
+    if (conv_validate_plan(&p, tuning, &base, &pl) != ITERMVS_OK || pl.backend != ITERMVS_CONV_TILE) {
+        printf("not a conv_tile layer\n");
+        return 1;
+    }
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    for (int i = 0; i < 3; ++i) itermvs_conv2d_tile(&p, H, W, 0);
+    for (int i = 0; i < 3; ++i) itermvs_conv2d_tile(base, &p, pl, tuning.persist, 0);
     (void)hipEventRecord(e0, 0);
-    for (int i = 0; i < 10; ++i) itermvs_conv2d_tile(&p, H, W, 0);
+    for (int i = 0; i < 10; ++i) itermvs_conv2d_tile(base, &p, pl, tuning.persist, 0);
     (void)hipEventRecord(e1, 0);
     (void)hipDeviceSynchronize();
     float ms = 0;
