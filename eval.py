@@ -86,6 +86,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "map is written.  memory (needs --dataset folder): each scan is fused from GPU memory as soon as its last "
                         "depth map is done -- no PFM is read back and no image is decoded twice (itermvs_amd.scan_fuse; ranks "
                         "take whole scans; the PLY is byte for byte the one of --fuse_points device)")
+    p.add_argument("--fuse_dedupe", action="store_true",
+                   help="--filter with the point cloud assembled on the GPU (--fuse_points device or --fuse_source memory): emit each "
+                        "surface point once per scan.  A pixel that an emitted point of an earlier reference view was verified against "
+                        "(the nearest pixel of a consistent reprojection, unless it lies across a depth edge) is dropped from its own "
+                        "view's vertices; what remains is a sub-sequence of the default cloud.  Off (default): every byte as before")
     p.add_argument("--no_pfm", action="store_true",
                    help="--fuse_source memory only: do not write the depth / confidence PFMs, only the PLY (and the masks of "
                         "--save_masks) reaches the disk")
@@ -195,11 +200,26 @@ def check_fuse_source(args) -> str:
     return source
 
 
+def check_fuse_dedupe(args) -> bool:
+    """--fuse_dedupe needs --filter and the GPU point assembly (--fuse_points device or --fuse_source memory)"""
+    if not getattr(args, "fuse_dedupe", False):
+        return False
+    on_gpu = getattr(args, "fuse_points", "host") == "device" or getattr(args, "fuse_source", "files") == "memory"
+    missing = [flag for flag, ok in (("--filter", bool(args.filter)), ("--fuse_points device or --fuse_source memory", on_gpu))
+               if not ok]
+    if missing:
+        raise SystemExit("--fuse_dedupe needs {} (the claim maps live on the GPU while a scan is fused), got {}--fuse_points {} "
+                         "--fuse_source {}".format(" and ".join(missing), "" if args.filter else "no --filter, ",
+                                                   getattr(args, "fuse_points", "host"), getattr(args, "fuse_source", "files")))
+    return True
+
+
 def fuse_memory(args) -> dict:
     """--fuse_source memory: depth maps and point clouds in one pass (itermvs_amd.scan_fuse); scans are sharded over the
     ranks whole, like ``fuse_scans`` shards them.  -> {scan: {ref_view: (geo, photo, final mask share)}} of this rank"""
     from itermvs_amd.scan_fuse import fuse_scans_from_memory
     check_fuse_source(args)
+    check_fuse_dedupe(args)
     check_feature_cache(args)
     rank, local_rank, world = shard.init_distributed()
     torch.cuda.set_device(local_rank)
@@ -305,6 +325,7 @@ def save_depth_folder(args, dataset, mine, model, dev) -> int:
 def fuse_scans(args) -> int:
     """eval.py:311-325: one point cloud per scan; scans are sharded over the ranks like the reference views"""
     from itermvs_amd import fusion
+    dedupe = check_fuse_dedupe(args)
     rank, local_rank, world = shard.init_distributed()
     dev = "cuda:%d" % local_rank
     scans = sorted(d for d in os.listdir(args.testpath)
@@ -316,7 +337,7 @@ def fuse_scans(args) -> int:
                                     os.path.join(args.outdir, scan + ".ply"), args.geo_pixel_thres, args.geo_depth_thres,
                                     args.photo_thres, geo_mask_thres=args.geo_mask_thres, device=dev, img_wh=tuple(args.img_wh),
                                     points=args.fuse_points,
-                                    save_masks=args.save_masks)
+                                    save_masks=args.save_masks, dedupe=dedupe)
         for v, (g, ph, f) in stats.items():
             print("processing {}, ref-view{:0>2}, geo_mask:{:3f} photo_mask:{:3f} final_mask: {:3f}".format(scan, v, g, ph, f))
         n += 1
@@ -327,6 +348,7 @@ def fuse_scans(args) -> int:
 if __name__ == "__main__":
     a = build_parser().parse_args()
     print("argv:", sys.argv[1:])
+    check_fuse_dedupe(a)
     if check_fuse_source(a) == "memory":
         fuse_memory(a)
     else:

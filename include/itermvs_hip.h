@@ -663,6 +663,32 @@ int itermvs_fuse_depth(const float* depth_ref, const float* conf_ref, const floa
                        void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * itermvs_fuse_depth_claim -- itermvs_fuse_depth with a claim step behind it, so that a surface point seen by N views is
+ *   emitted once per scan (eval.py --fuse_dedupe).  The caller keeps one map claimed[v], uint8 [H,W], per view of the scan, all
+ *   zero at the start of the scan, and fuses the reference views in pair.txt order on one stream.  For reference view r, pixel p:
+ *   1. depth_avg, photo, geo, the count and per source s the consistency decision ok_s are those of itermvs_fuse_depth, bit for
+ *      bit (eval.py:238-269; same per-pixel code).
+ *   2. final[p] = photo && geo && claimed_ref[p] == 0.  photo_mask and geo_mask are unchanged; final_mask is the emit mask.
+ *   3. If final[p], for every source s with ok_s: with (xs, ys) the fp32 source coordinates of p and smp the fp32 bilinear
+ *      sample of depth_src[s] there (both as in step 1), qx = rintf(xs), qy = rintf(ys); if 0 <= qx <= W-1 and 0 <= qy <= H-1
+ *      (compared in fp32, so NaN and inf fail) and fabsf(depth_src[s][qy*W+qx] - smp) / smp < geo_depth_thres in fp32 (false
+ *      or NaN: no claim), then claimed_src[s][qy*W+qx] = 1.  The second condition keeps a nearest pixel that lies across a depth
+ *      edge from being suppressed by a point it does not represent.
+ *   Step 3 has no counterpart in the reference (it is the used-pixel marking of Gipuma's fusibile); steps 1 and 2 with all maps
+ *   zero are eval.py:238-269.  The vertices are what itermvs_fuse_points makes of depth_avg and this final_mask.
+ * claimed_ref: device [H,W] uint8, read only; NULL = all zero.  claimed_src: HOST array of S device pointers to [H,W] uint8
+ *   maps, only ever written, with plain byte stores of the constant 1 (no atomics, no order between workgroups: the result does
+ *   not depend on scheduling); NULL = step 3 is skipped.  Every other argument as in itermvs_fuse_depth, same launch shape.
+ * Validation before the launch: the checks of itermvs_fuse_depth, then ITERMVS_ERR_NULL for a NULL entry of claimed_src and
+ *   ITERMVS_ERR_DIMS when a claimed_src[s] == claimed_ref (the launch would race with itself; r is never its own source).
+ * ------------------------------------------------------------------------------------------ */
+int itermvs_fuse_depth_claim(const float* depth_ref, const float* conf_ref, const float* const* depth_src,
+                             const float* mats, int32_t S, int32_t H, int32_t W, double geo_pixel_thres,
+                             float geo_depth_thres, float photo_thres, int32_t geo_mask_thres, double* depth_avg,
+                             uint8_t* photo_mask, uint8_t* geo_mask, uint8_t* final_mask, int32_t* geo_sum,
+                             const uint8_t* claimed_ref, uint8_t* const* claimed_src, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * itermvs_fuse_points -- the tail of filter_depth for ONE reference view (eval.py:287-308): the pixels of `final_mask` are
  *   unprojected (eval.py:287-294), coloured (eval.py:295-296) and appended to `records` as the PLY vertex element of
  *   eval.py:298-308 (x, y, z little-endian float32; red, green, blue uint8: 15 bytes per vertex, unpadded), in row-major pixel

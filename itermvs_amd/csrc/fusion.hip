@@ -7,6 +7,8 @@
 // float32 (inverted / composed on the host exactly like eval.py does), every product with a point in float64;
 // cv2.remap(INTER_LINEAR) as published (1/32-pixel coordinates, float32 weights, zero border).  oracle/fusion_oracle.py
 // is the CPU restatement the tests compare against, bit for bit.
+// itermvs_fuse_depth_claim is the same per-pixel body (fuse_pixel<true>) with the claim step of include/itermvs_hip.h behind it:
+// a pixel that another view's emitted point was verified against is marked and never emits a copy of that point.
 #include <math.h>
 
 #include "common.hpp"
@@ -63,7 +65,28 @@ __device__ __forceinline__ float remap_bilinear(const float* __restrict__ src, i
     return out;
 }
 
-__global__ void __launch_bounds__(256) fuse_depth_kernel(const FuseArgs a) {
+struct FuseClaimArgs {
+    FuseArgs f;
+    const uint8_t* claimed_ref;                  // [H,W] of the reference view, or null: nothing is claimed yet
+    uint8_t* claimed_src[ITERMVS_MAX_SRC];       // [H,W] per source view; claimed_src[0] null: the claim step is skipped
+};
+
+// reference pixel (px, py, d) = (x * d, y * d, d) -> its position in the source view of `m`, float64   (eval.py:162-169)
+__device__ __forceinline__ void project_to_source(const float* __restrict__ m, double px, double py, double d, double& xs,
+                                                  double& ys) {
+    double rx, ry, rz, sx, sy, sz, kx, ky, kz;
+    mat3(m, px, py, d, rx, ry, rz);                    // reference 3-D space      (eval.py:162-163)
+    mat34(m + 9, rx, ry, rz, sx, sy, sz);              // source 3-D space         (eval.py:165-166)
+    mat3(m + 21, sx, sy, sz, kx, ky, kz);              // source pixel             (eval.py:168-169)
+    xs = kx / kz;
+    ys = ky / kz;
+}
+
+// One reference pixel.  Claim = false is itermvs_fuse_depth; Claim = true adds the two places where the claim maps enter: the
+// pixel's own mark gates `final`, and an emitting pixel marks the source pixel nearest to each consistent reprojection.
+template <bool Claim>
+__device__ __forceinline__ void fuse_pixel(const FuseArgs& a, const uint8_t* __restrict__ claimed_ref,
+                                           uint8_t* const* claimed_src) {
     const int x = blockIdx.x * 32 + (threadIdx.x & 31);
     const int y = blockIdx.y * 8 + (threadIdx.x >> 5);
     if (x >= a.W || y >= a.H) return;
@@ -72,14 +95,12 @@ __global__ void __launch_bounds__(256) fuse_depth_kernel(const FuseArgs a) {
     const double d = (double)dref;
     const double px = (double)x * d, py = (double)y * d;
     int geo = 0;
+    uint32_t ok_bits = 0;
     float acc = 0.0f;
     for (int s = 0; s < a.S; ++s) {
         const float* __restrict__ m = a.mats + s * 60;
-        double rx, ry, rz, sx, sy, sz, kx, ky, kz;
-        mat3(m, px, py, d, rx, ry, rz);                    // reference 3-D space      (eval.py:162-163)
-        mat34(m + 9, rx, ry, rz, sx, sy, sz);              // source 3-D space         (eval.py:165-166)
-        mat3(m + 21, sx, sy, sz, kx, ky, kz);              // source pixel             (eval.py:168-169)
-        const double xs = kx / kz, ys = ky / kz;
+        double xs, ys;
+        project_to_source(m, px, py, d, xs, ys);
         const float xs32 = (float)xs, ys32 = (float)ys;
         const double smp = (double)remap_bilinear(a.depth_src[s], a.H, a.W, xs32, ys32);   // eval.py:176
         double qx, qy, qz, wx, wy, wz, jx, jy, jz;
@@ -93,30 +114,57 @@ __global__ void __launch_bounds__(256) fuse_depth_kernel(const FuseArgs a) {
         const float rel = fabsf(drep - dref) / dref;                                        // eval.py:205-206
         const bool ok = dist < a.geo_pixel_thres && rel < a.geo_depth_thres;
         geo += ok ? 1 : 0;
+        if (Claim) ok_bits |= (ok ? 1u : 0u) << s;
         acc = acc + (ok ? drep : 0.0f);                                                     // eval.py:209,262
     }
     const float total = acc + dref;
     a.depth_avg[p] = (double)total / (double)(geo + 1);                                    // eval.py:264
     const bool photo = a.conf_ref[p] > a.photo_thres, g = geo >= a.geo_mask_thres;
+    bool final = photo && g;
+    if (Claim) final = final && !(claimed_ref && claimed_ref[p] != 0);
     if (a.photo_mask) a.photo_mask[p] = photo;
     if (a.geo_mask) a.geo_mask[p] = g;
-    if (a.final_mask) a.final_mask[p] = photo && g;
+    if (a.final_mask) a.final_mask[p] = final;
     if (a.geo_sum) a.geo_sum[p] = geo;
+    if (!Claim || !final || !claimed_src[0]) return;
+    // The claim step, for the few pixels that emit: the projection and the sample of each consistent source are computed again
+    // by the expressions above (same operations, same bits) instead of being held in registers for all S sources.
+    const float wmax = (float)(a.W - 1), hmax = (float)(a.H - 1);
+    for (int s = 0; s < a.S; ++s) {
+        if (!((ok_bits >> s) & 1u)) continue;
+        double xs, ys;
+        project_to_source(a.mats + s * 60, px, py, d, xs, ys);
+        const float xs32 = (float)xs, ys32 = (float)ys;
+        const float smp32 = remap_bilinear(a.depth_src[s], a.H, a.W, xs32, ys32);
+        const float qx = rintf(xs32), qy = rintf(ys32);
+        if (!(qx >= 0.0f && qx <= wmax && qy >= 0.0f && qy <= hmax)) continue;             // NaN and inf fail: q is inside [H,W]
+        const size_t q = (size_t)(int)qy * (size_t)a.W + (size_t)(int)qx;
+        if (fabsf(a.depth_src[s][q] - smp32) / smp32 < a.geo_depth_thres) claimed_src[s][q] = 1;   // not across a depth edge
+    }
+}
+
+__global__ void __launch_bounds__(256) fuse_depth_kernel(const FuseArgs a) {
+    fuse_pixel<false>(a, nullptr, nullptr);
+}
+
+// Reads claimed_ref, writes claimed_src[s] (never the same map: checked on the host) with plain byte stores of the constant 1:
+// whichever threads reach a byte, in whatever order, it ends as 1, so the maps do not depend on scheduling and need no atomics.
+__global__ void __launch_bounds__(256) fuse_depth_claim_kernel(const FuseClaimArgs c) {
+    fuse_pixel<true>(c.f, c.claimed_ref, c.claimed_src);
 }
 
 }  // namespace itermvs
 
 using namespace itermvs;
 
-extern "C" int itermvs_fuse_depth(const float* depth_ref, const float* conf_ref, const float* const* depth_src,
-                                  const float* mats, int32_t S, int32_t H, int32_t W, double geo_pixel_thres,
-                                  float geo_depth_thres, float photo_thres, int32_t geo_mask_thres, double* depth_avg,
-                                  uint8_t* photo_mask, uint8_t* geo_mask, uint8_t* final_mask, int32_t* geo_sum,
-                                  void* stream) {
+// the checks and the argument block both entry points share
+static int fill_fuse_args(FuseArgs& a, const float* depth_ref, const float* conf_ref, const float* const* depth_src,
+                          const float* mats, int32_t S, int32_t H, int32_t W, double geo_pixel_thres, float geo_depth_thres,
+                          float photo_thres, int32_t geo_mask_thres, double* depth_avg, uint8_t* photo_mask, uint8_t* geo_mask,
+                          uint8_t* final_mask, int32_t* geo_sum) {
     ITERMVS_RETURN_IF(!depth_ref || !conf_ref || !depth_src || !mats || !depth_avg, ITERMVS_ERR_NULL);
     ITERMVS_RETURN_IF(H < 1 || W < 1, ITERMVS_ERR_DIMS);
     ITERMVS_RETURN_IF(S < 1 || S > ITERMVS_MAX_SRC, ITERMVS_ERR_VIEWS);
-    FuseArgs a;
     a.depth_ref = depth_ref; a.conf_ref = conf_ref; a.mats = mats;
     for (int s = 0; s < ITERMVS_MAX_SRC; ++s) {
         a.depth_src[s] = s < S ? depth_src[s] : nullptr;
@@ -126,6 +174,38 @@ extern "C" int itermvs_fuse_depth(const float* depth_ref, const float* conf_ref,
     a.geo_sum = geo_sum;
     a.S = S; a.H = H; a.W = W; a.geo_mask_thres = geo_mask_thres;
     a.geo_pixel_thres = geo_pixel_thres; a.geo_depth_thres = geo_depth_thres; a.photo_thres = photo_thres;
+    return ITERMVS_OK;
+}
+
+extern "C" int itermvs_fuse_depth(const float* depth_ref, const float* conf_ref, const float* const* depth_src,
+                                  const float* mats, int32_t S, int32_t H, int32_t W, double geo_pixel_thres,
+                                  float geo_depth_thres, float photo_thres, int32_t geo_mask_thres, double* depth_avg,
+                                  uint8_t* photo_mask, uint8_t* geo_mask, uint8_t* final_mask, int32_t* geo_sum,
+                                  void* stream) {
+    FuseArgs a;
+    const int status = fill_fuse_args(a, depth_ref, conf_ref, depth_src, mats, S, H, W, geo_pixel_thres, geo_depth_thres,
+                                      photo_thres, geo_mask_thres, depth_avg, photo_mask, geo_mask, final_mask, geo_sum);
+    if (status != ITERMVS_OK) return status;
     hipLaunchKernelGGL(fuse_depth_kernel, dim3((W + 31) / 32, (H + 7) / 8), dim3(256), 0, (hipStream_t)stream, a);
+    return itermvs_launch_status();
+}
+
+extern "C" int itermvs_fuse_depth_claim(const float* depth_ref, const float* conf_ref, const float* const* depth_src,
+                                        const float* mats, int32_t S, int32_t H, int32_t W, double geo_pixel_thres,
+                                        float geo_depth_thres, float photo_thres, int32_t geo_mask_thres, double* depth_avg,
+                                        uint8_t* photo_mask, uint8_t* geo_mask, uint8_t* final_mask, int32_t* geo_sum,
+                                        const uint8_t* claimed_ref, uint8_t* const* claimed_src, void* stream) {
+    FuseClaimArgs c;
+    const int status = fill_fuse_args(c.f, depth_ref, conf_ref, depth_src, mats, S, H, W, geo_pixel_thres, geo_depth_thres,
+                                      photo_thres, geo_mask_thres, depth_avg, photo_mask, geo_mask, final_mask, geo_sum);
+    if (status != ITERMVS_OK) return status;
+    c.claimed_ref = claimed_ref;
+    for (int s = 0; s < ITERMVS_MAX_SRC; ++s) {
+        c.claimed_src[s] = claimed_src && s < S ? claimed_src[s] : nullptr;
+        ITERMVS_RETURN_IF(claimed_src && s < S && !claimed_src[s], ITERMVS_ERR_NULL);
+        // a map that is read as claimed_ref and written as claimed_src in one launch would race with itself
+        ITERMVS_RETURN_IF(claimed_src && s < S && claimed_src[s] == claimed_ref, ITERMVS_ERR_DIMS);
+    }
+    hipLaunchKernelGGL(fuse_depth_claim_kernel, dim3((W + 31) / 32, (H + 7) / 8), dim3(256), 0, (hipStream_t)stream, c);
     return itermvs_launch_status();
 }

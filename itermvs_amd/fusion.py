@@ -162,7 +162,7 @@ def _download(records: torch.Tensor, nbytes: int, write, seconds: Dict[str, floa
 def fuse_scan(pairs: Sequence[Tuple[int, Sequence[int]]], cams, depths, confidences, images, plyfilename: str,
               geo_pixel_thres: float, geo_depth_thres: float, photo_thres: float, geo_mask_thres: int = 3, device: str = "cuda",
               records_budget: int = 2 << 30, mask_folder: str = None, group_capacity: int = None,
-              info: dict = None) -> Dict[int, Tuple[float, float, float]]:
+              info: dict = None, dedupe: bool = False) -> Dict[int, Tuple[float, float, float]]:
     """eval.py:215-309 for a scan that is already in memory, with the point cloud assembled on the GPU: per reference view one
     ``itermvs_fuse_depth`` and one ``itermvs_fuse_points``, enqueued back to back; the host synchronises once per GROUP of
     reference views, downloads the group's finished vertex records and appends them to the PLY.
@@ -173,6 +173,10 @@ def fuse_scan(pairs: Sequence[Tuple[int, Sequence[int]]], cams, depths, confiden
     group fits even if every pixel survives.  group_capacity: vertices the buffer holds instead of that worst case (a group
     that emits more raises).  mask_folder: write the three masks of every reference view there (eval.py:266-269).
     info: filled with the groups, the number of synchronisations / downloads and where the time went.
+    dedupe: emit each surface point once per scan (``itermvs_fuse_depth_claim`` in place of ``itermvs_fuse_depth``): one zeroed
+    uint8 [H,W] claim map per view lives on the GPU for the whole scan, across the flush groups; a pixel that an emitted point of an
+    earlier reference view was verified against is left out of ``final``.  The vertices are a sub-sequence of the ones without
+    it.  The final mask share of the result and the final masks of ``mask_folder`` are those of the emit mask.
     -> {ref_view: (geo, photo, final mask share)} like ``filter_depth``."""
     dev = torch.device(device)
     clock = time.perf_counter
@@ -188,6 +192,7 @@ def fuse_scan(pairs: Sequence[Tuple[int, Sequence[int]]], cams, depths, confiden
                 if v not in on_dev:
                     on_dev[v] = as_t(depths[v], torch.float32)
         h, w = on_dev[pairs[0][0]].shape if pairs else (1, 1)
+        claimed = {v: torch.zeros((h, w), device=dev, dtype=torch.uint8) for v in on_dev} if dedupe else None
         conf = [as_t(confidences[ref], torch.float32) for ref, _ in pairs]
         rgb = [as_t(images[ref], torch.uint8) for ref, _ in pairs]
         for ref, t in zip((p[0] for p in pairs), rgb):
@@ -220,9 +225,12 @@ def fuse_scan(pairs: Sequence[Tuple[int, Sequence[int]]], cams, depths, confiden
                 masks = []
                 for i in range(a, b):
                     ref, srcs = pairs[i]
-                    avg, photo, geo, final, _ = ops.fuse_depth(on_dev[ref], conf[i], [on_dev[v] for v in srcs],
-                                                               mats[first_mat[i]:first_mat[i + 1]], geo_pixel_thres,
-                                                               geo_depth_thres, photo_thres, geo_mask_thres)
+                    maps = (on_dev[ref], conf[i], [on_dev[v] for v in srcs], mats[first_mat[i]:first_mat[i + 1]])
+                    thres = (geo_pixel_thres, geo_depth_thres, photo_thres, geo_mask_thres)
+                    if dedupe:
+                        avg, photo, geo, final, _ = ops.fuse_depth_claim(*maps, claimed[ref], [claimed[v] for v in srcs], *thres)
+                    else:
+                        avg, photo, geo, final, _ = ops.fuse_depth(*maps, *thres)
                     ops.fuse_points(avg, final, cam[i], rgb[i], records, cursor, counts, i, photo, geo, capacity, workspace)
                     if mask_folder is not None:
                         masks.append((ref, photo, geo, final))
@@ -259,14 +267,15 @@ def fuse_scan(pairs: Sequence[Tuple[int, Sequence[int]]], cams, depths, confiden
                 f.write(ply_header(0))
     if info is not None:
         info.update(groups=groups, synchronisations=n_sync, downloads=len(groups), download_chunks=n_chunks,
-                    vertices=n_vertices, capacity=capacity, seconds=seconds)
+                    vertices=n_vertices, capacity=capacity, seconds=seconds, dedupe=bool(dedupe))
     return stats
 
 
 def filter_depth(scan_folder: str, out_folder: str, plyfilename: str, geo_pixel_thres: float, geo_depth_thres: float,
                  photo_thres: float, images: Dict[int, np.ndarray] = None, intrinsics_scale: Tuple[float, float] = None,
                  geo_mask_thres: int = 3, device: str = "cuda", img_wh: Tuple[int, int] = None, points: str = "host",
-                 save_masks: bool = False, records_budget: int = 2 << 30, info: dict = None) -> Dict[str, float]:
+                 save_masks: bool = False, records_budget: int = 2 << 30, info: dict = None,
+                 dedupe: bool = False) -> Dict[str, float]:
     """eval.py:215-309: for every reference view of ``pair.txt`` fuse its depth map with its source views' and append the
     surviving pixels to one point cloud.
 
@@ -281,9 +290,13 @@ def filter_depth(scan_folder: str, out_folder: str, plyfilename: str, geo_pixel_
     view.  "device": ``fuse_scan`` -- the same files are read, the vertex records are built by ``itermvs_fuse_points`` and the
     host synchronises once per group of reference views (``records_budget`` bytes of records per group; ``info`` as in
     ``fuse_scan``); same header, vertex order and colours, coordinates equal up to the last float64 bit of ``np.matmul``.
-    ``save_masks``: also write ``<out_folder>/mask/{view:0>8}_photo.png``, ``_geo.png``, ``_final.png`` (eval.py:266-269)."""
+    ``save_masks``: also write ``<out_folder>/mask/{view:0>8}_photo.png``, ``_geo.png``, ``_final.png`` (eval.py:266-269).
+    ``dedupe``: ``fuse_scan``'s, so it needs ``points="device"``."""
     if points not in ("host", "device"):
         raise ValueError(f"filter_depth: points must be 'host' or 'device', got {points!r}")
+    if dedupe and points != "device":
+        raise ValueError("filter_depth: dedupe=True needs points='device' (the claim maps live on the GPU between the reference "
+                         f"views), got points={points!r}")
     pairs = read_pair_file(os.path.join(scan_folder, "pair.txt"))
     mask_folder = os.path.join(out_folder, "mask") if save_masks else None
     if img_wh is None and images is None and intrinsics_scale is None:
@@ -339,7 +352,7 @@ def filter_depth(scan_folder: str, out_folder: str, plyfilename: str, geo_pixel_
             else:
                 rgb[ref_view] = pixels.pop(ref_view) if ref_view in pixels else np.full((h, w, 3), 127, np.uint8)
         return fuse_scan(pairs, cams, depths, confs, rgb, plyfilename, geo_pixel_thres, geo_depth_thres, photo_thres,
-                         geo_mask_thres, device, records_budget, mask_folder, info=info)
+                         geo_mask_thres, device, records_budget, mask_folder, info=info, dedupe=dedupe)
 
     vertexs, colors, stats = [], [], {}
     for ref_view, src_views in pairs:

@@ -1304,27 +1304,57 @@ def conv2d(x: Tensor, weight, bias=None, *, ksize: int = 3, stride: int = 1, pad
 CONV_FLOP_COUNTER = {"enabled": False, "flops": 0.0, "launches": 0}
 
 
-def fuse_depth(depth_ref: Tensor, conf_ref: Tensor, depth_src: Sequence[Tensor], mats: Tensor, geo_pixel_thres: float = 1.0,
-               geo_depth_thres: float = 0.01, photo_thres: float = 0.3, geo_mask_thres: int = 3):
-    """itermvs_fuse_depth (eval.py:154-269 for one reference view).  depth_ref / conf_ref [H,W], depth_src: S maps [H,W],
-    mats [S,60] (itermvs_amd.fusion.pair_matrices).  -> (depth_avg float64 [H,W], photo, geo, final uint8, count int32)."""
+def _fuse_depth(what: str, depth_ref: Tensor, conf_ref: Tensor, depth_src: Sequence[Tensor], mats: Tensor, geo_pixel_thres: float,
+                geo_depth_thres: float, photo_thres: float, geo_mask_thres: int, claim: Optional[tuple] = None):
+    """the inputs, outputs and call that itermvs_fuse_depth and itermvs_fuse_depth_claim share; ``claim``: the two extra pointer
+    arguments of the latter"""
     h, w = depth_ref.shape
     s = len(depth_src)
     depth_ref, conf_ref = _dev(depth_ref, "depth_ref").contiguous(), _dev(conf_ref, "conf_ref").contiguous()
     srcs = [_dev(t, "depth_src").contiguous() for t in depth_src]
     if any(tuple(t.shape) != (h, w) for t in srcs + [conf_ref]) or tuple(mats.shape) != (s, 60):
-        raise RuntimeError("fuse_depth: all maps must be [H,W] and mats [S,60]")
+        raise RuntimeError(f"{what}: all maps must be [H,W] and mats [S,60]")
     mats = _dev(mats, "mats").float().contiguous()
     ptrs = (C.c_void_p * s)(*[t.data_ptr() for t in srcs])
     dev = depth_ref.device
     avg = torch.empty((h, w), device=dev, dtype=torch.float64)
     photo, geo, final = (torch.empty((h, w), device=dev, dtype=torch.uint8) for _ in range(3))
     cnt = torch.empty((h, w), device=dev, dtype=torch.int32)
-    check(_lib.load().itermvs_fuse_depth(depth_ref.data_ptr(), conf_ref.data_ptr(), ptrs, mats.data_ptr(), s, h, w,
-                                         float(geo_pixel_thres), float(geo_depth_thres), float(photo_thres), int(geo_mask_thres),
-                                         avg.data_ptr(), photo.data_ptr(), geo.data_ptr(), final.data_ptr(), cnt.data_ptr(),
-                                         _stream()), "itermvs_fuse_depth")
+    check(getattr(_lib.load(), "itermvs_" + what)(depth_ref.data_ptr(), conf_ref.data_ptr(), ptrs, mats.data_ptr(), s, h, w,
+                                                  float(geo_pixel_thres), float(geo_depth_thres), float(photo_thres),
+                                                  int(geo_mask_thres), avg.data_ptr(), photo.data_ptr(), geo.data_ptr(),
+                                                  final.data_ptr(), cnt.data_ptr(), *(claim or ()), _stream()), "itermvs_" + what)
     return avg, photo, geo, final, cnt
+
+
+def fuse_depth(depth_ref: Tensor, conf_ref: Tensor, depth_src: Sequence[Tensor], mats: Tensor, geo_pixel_thres: float = 1.0,
+               geo_depth_thres: float = 0.01, photo_thres: float = 0.3, geo_mask_thres: int = 3):
+    """itermvs_fuse_depth (eval.py:154-269 for one reference view).  depth_ref / conf_ref [H,W], depth_src: S maps [H,W],
+    mats [S,60] (itermvs_amd.fusion.pair_matrices).  -> (depth_avg float64 [H,W], photo, geo, final uint8, count int32)."""
+    return _fuse_depth("fuse_depth", depth_ref, conf_ref, depth_src, mats, geo_pixel_thres, geo_depth_thres, photo_thres,
+                       geo_mask_thres)
+
+
+def fuse_depth_claim(depth_ref: Tensor, conf_ref: Tensor, depth_src: Sequence[Tensor], mats: Tensor,
+                     claimed_ref: Optional[Tensor], claimed_src: Optional[Sequence[Tensor]], geo_pixel_thres: float = 1.0,
+                     geo_depth_thres: float = 0.01, photo_thres: float = 0.3, geo_mask_thres: int = 3):
+    """itermvs_fuse_depth_claim: ``fuse_depth`` whose ``final`` leaves out the pixels marked in ``claimed_ref`` (uint8 [H,W];
+    None: nothing is marked), and whose emitting pixels mark, IN PLACE, the pixel they were verified against in each consistent
+    source view's map of ``claimed_src`` (S uint8 [H,W] maps, none of them ``claimed_ref``; None: nothing is marked).  The
+    contract is in include/itermvs_hip.h.  -> the tuple of ``fuse_depth``."""
+    h, w = depth_ref.shape
+    maps = ([] if claimed_ref is None else [claimed_ref]) + list(claimed_src or [])
+    for t in maps:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError("fuse_depth_claim: expected CUDA/ROCm tensors - the IterMVS HIP engine has no CPU path")
+        if t.dtype != torch.uint8 or tuple(t.shape) != (h, w) or not t.is_contiguous() or t.device != depth_ref.device:
+            raise RuntimeError(f"fuse_depth_claim: a claim map must be a contiguous torch.uint8 tensor of shape {(h, w)} on "
+                               f"{depth_ref.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    if claimed_src is not None and len(claimed_src) != len(depth_src):
+        raise RuntimeError(f"fuse_depth_claim: {len(claimed_src)} claim maps for {len(depth_src)} source views")
+    ptrs = None if claimed_src is None else (C.c_void_p * len(claimed_src))(*[t.data_ptr() for t in claimed_src])
+    return _fuse_depth("fuse_depth_claim", depth_ref, conf_ref, depth_src, mats, geo_pixel_thres, geo_depth_thres, photo_thres,
+                       geo_mask_thres, claim=(None if claimed_ref is None else claimed_ref.data_ptr(), ptrs))
 
 
 POINT_RECORD_BYTES = 15      # PLY vertex of eval.py:298-308: x, y, z float32, red, green, blue uint8

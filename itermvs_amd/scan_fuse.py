@@ -246,7 +246,8 @@ def fuse_scans_from_memory(args, dataset, scans: Sequence[str], model, dev) -> D
             mask_folder = os.path.join(args.outdir, scan, "mask") if getattr(args, "save_masks", False) else None
             stats[scan] = fusion.fuse_scan(pairs, cams, store.depth, store.conf, store.rgb,
                                            os.path.join(args.outdir, scan + ".ply"), args.geo_pixel_thres, args.geo_depth_thres,
-                                           args.photo_thres, args.geo_mask_thres, str(dev), mask_folder=mask_folder)
+                                           args.photo_thres, args.geo_mask_thres, str(dev), mask_folder=mask_folder,
+                                           dedupe=bool(getattr(args, "fuse_dedupe", False)))
             for v, (g, ph, f) in stats[scan].items():
                 print("processing {}, ref-view{:0>2}, geo_mask:{:3f} photo_mask:{:3f} final_mask: {:3f}".format(scan, v, g, ph, f))
             del store
