@@ -91,6 +91,17 @@ def build_parser() -> argparse.ArgumentParser:
                         "surface point once per scan.  A pixel that an emitted point of an earlier reference view was verified against "
                         "(the nearest pixel of a consistent reprojection, unless it lies across a depth edge) is dropped from its own "
                         "view's vertices; what remains is a sub-sequence of the default cloud.  Off (default): every byte as before")
+    p.add_argument("--ply_normals", action="store_true",
+                   help="--filter with the point cloud assembled on the GPU (--fuse_points device or --fuse_source memory): every "
+                        "PLY vertex carries nx ny nz between z and red (the layout of COLMAP's fused.ply), the unit normal of the "
+                        "surface at the pixel: the cross product of the fused depth map's differences to the neighbouring pixels "
+                        "along the row and the column, in world space, facing the reference camera that saw the point; (0, 0, 0) "
+                        "where no neighbour on the same surface exists.  Off (default): every byte as before")
+    p.add_argument("--normal_edge_thres", type=float, default=0.01,
+                   help="--ply_normals: a neighbouring pixel whose fused depth differs by this share of the pixel's depth or more "
+                        "lies across a depth edge and is not used for the normal.  The default is the step --geo_depth_thres "
+                        "already treats as another surface (at 640 px wide it still admits surfaces slanted by about 85 degrees); "
+                        "a choice, not a measured optimum")
     p.add_argument("--no_pfm", action="store_true",
                    help="--fuse_source memory only: do not write the depth / confidence PFMs, only the PLY (and the masks of "
                         "--save_masks) reaches the disk")
@@ -200,17 +211,33 @@ def check_fuse_source(args) -> str:
     return source
 
 
-def check_fuse_dedupe(args) -> bool:
-    """--fuse_dedupe needs --filter and the GPU point assembly (--fuse_points device or --fuse_source memory)"""
-    if not getattr(args, "fuse_dedupe", False):
+def _check_gpu_assembly_flag(args, name: str, flag: str, why: str) -> bool:
+    """a flag of the GPU point assembly needs --filter and --fuse_points device or --fuse_source memory"""
+    if not getattr(args, name, False):
         return False
     on_gpu = getattr(args, "fuse_points", "host") == "device" or getattr(args, "fuse_source", "files") == "memory"
-    missing = [flag for flag, ok in (("--filter", bool(args.filter)), ("--fuse_points device or --fuse_source memory", on_gpu))
+    missing = [f for f, ok in (("--filter", bool(args.filter)), ("--fuse_points device or --fuse_source memory", on_gpu))
                if not ok]
     if missing:
-        raise SystemExit("--fuse_dedupe needs {} (the claim maps live on the GPU while a scan is fused), got {}--fuse_points {} "
-                         "--fuse_source {}".format(" and ".join(missing), "" if args.filter else "no --filter, ",
+        raise SystemExit("{} needs {} ({}), got {}--fuse_points {} "
+                         "--fuse_source {}".format(flag, " and ".join(missing), why, "" if args.filter else "no --filter, ",
                                                    getattr(args, "fuse_points", "host"), getattr(args, "fuse_source", "files")))
+    return True
+
+
+def check_fuse_dedupe(args) -> bool:
+    """--fuse_dedupe needs --filter and the GPU point assembly (--fuse_points device or --fuse_source memory)"""
+    return _check_gpu_assembly_flag(args, "fuse_dedupe", "--fuse_dedupe", "the claim maps live on the GPU while a scan is fused")
+
+
+def check_ply_normals(args) -> bool:
+    """--ply_normals needs --filter and the GPU point assembly, and --normal_edge_thres a finite value above 0"""
+    if not _check_gpu_assembly_flag(args, "ply_normals", "--ply_normals",
+                                    "the normals are computed on the GPU while the vertices are emitted"):
+        return False
+    edge = getattr(args, "normal_edge_thres", 0.01)
+    if not 0 < edge < float("inf"):
+        raise SystemExit(f"--normal_edge_thres must be a finite share of the depth above 0, got {edge}")
     return True
 
 
@@ -220,6 +247,7 @@ def fuse_memory(args) -> dict:
     from itermvs_amd.scan_fuse import fuse_scans_from_memory
     check_fuse_source(args)
     check_fuse_dedupe(args)
+    check_ply_normals(args)
     check_feature_cache(args)
     rank, local_rank, world = shard.init_distributed()
     torch.cuda.set_device(local_rank)
@@ -326,6 +354,7 @@ def fuse_scans(args) -> int:
     """eval.py:311-325: one point cloud per scan; scans are sharded over the ranks like the reference views"""
     from itermvs_amd import fusion
     dedupe = check_fuse_dedupe(args)
+    normals = check_ply_normals(args)
     rank, local_rank, world = shard.init_distributed()
     dev = "cuda:%d" % local_rank
     scans = sorted(d for d in os.listdir(args.testpath)
@@ -337,7 +366,8 @@ def fuse_scans(args) -> int:
                                     os.path.join(args.outdir, scan + ".ply"), args.geo_pixel_thres, args.geo_depth_thres,
                                     args.photo_thres, geo_mask_thres=args.geo_mask_thres, device=dev, img_wh=tuple(args.img_wh),
                                     points=args.fuse_points,
-                                    save_masks=args.save_masks, dedupe=dedupe)
+                                    save_masks=args.save_masks, dedupe=dedupe, normals=normals,
+                                    normal_edge_thres=getattr(args, "normal_edge_thres", 0.01))
         for v, (g, ph, f) in stats.items():
             print("processing {}, ref-view{:0>2}, geo_mask:{:3f} photo_mask:{:3f} final_mask: {:3f}".format(scan, v, g, ph, f))
         n += 1
@@ -349,6 +379,7 @@ if __name__ == "__main__":
     a = build_parser().parse_args()
     print("argv:", sys.argv[1:])
     check_fuse_dedupe(a)
+    check_ply_normals(a)
     if check_fuse_source(a) == "memory":
         fuse_memory(a)
     else:

@@ -718,6 +718,33 @@ int itermvs_fuse_points(const double* depth_avg, const uint8_t* final_mask, cons
                         uint32_t* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * itermvs_fuse_points_normals -- itermvs_fuse_points with an oriented unit normal per vertex (eval.py --ply_normals; no
+ *   counterpart in the reference, the vertex layout is COLMAP's fused.ply).  Records are 27 bytes, unpadded: x, y, z, nx, ny, nz
+ *   little-endian float32, then red, green, blue uint8.  x, y, z and the colour are itermvs_fuse_points' (the same device code);
+ *   every argument, the workspace, the capacity rule (nothing outside records[0 : 27 * capacity] is written), cursor, view_counts
+ *   and the three launches (the same count and scan kernels, an emit kernel of its own; no atomics, no workgroup waits on
+ *   another) are as there.
+ * The normal of pixel p = (x, y), all in fp64 without fused multiply-add, sums in the written order, IEEE sqrt and division:
+ *   1. d = depth_avg[p]; d not finite or d <= 0: the normal is (0,0,0) (the vertex is emitted all the same).
+ *   2. Pc(q) = inv(K_ref) (xq*dq, yq*dq, dq): the camera-space point itermvs_fuse_points computes on its way to x, y, z.
+ *   3. A neighbour q is usable iff it is inside the image, dq is finite and > 0 and fabs(dq - d) < edge_thres * d (false for
+ *      NaN).  It need not be in final_mask: depth_avg is defined at every pixel.  Left / right are tested on the row: x = 0 has no
+ *      left and x = W-1 no right neighbour.
+ *   4. tx = Pc(x+1,y) - Pc(x-1,y) when both are usable, Pc(x+1,y) - Pc(p) or Pc(p) - Pc(x-1,y) when one is, and the normal is
+ *      (0,0,0) when neither is; ty likewise with y+1, y-1.
+ *   5. nc = (tx.y*ty.z - tx.z*ty.y, tx.z*ty.x - tx.x*ty.z, tx.x*ty.y - tx.y*ty.x).
+ *   6. s = (nc.x*Pc.x + nc.y*Pc.y) + nc.z*Pc.z at p; s > 0: nc = -nc, so the normal faces the camera that saw the point.
+ *   7. To world space with the 3x3 part of inv(E_ref), cam[9+0..2], cam[9+4..6], cam[9+8..10] upcast: (m0*a + m1*b) + m2*c.
+ *   8. len = sqrt((nx*nx + ny*ny) + nz*nz); len not finite or not > 0: (0,0,0); else each component / len, converted to fp32 once.
+ * edge_thres: relative depth step beyond which a neighbour is another surface (eval.py's default 0.01).
+ * Validation before the launch: the checks of itermvs_fuse_points, then ITERMVS_ERR_DIMS unless edge_thres is finite and > 0.
+ * ------------------------------------------------------------------------------------------ */
+int itermvs_fuse_points_normals(const double* depth_avg, const uint8_t* final_mask, const uint8_t* photo_mask,
+                                const uint8_t* geo_mask, const float* cam, const uint8_t* rgb, int32_t H, int32_t W,
+                                double edge_thres, uint8_t* records, int64_t capacity, uint64_t* cursor,
+                                int64_t* view_counts, int32_t view, uint32_t* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The COLMAP converter's two device stages (csrc/colmap.hip; colmap_input.py of the reference, host side: itermvs_amd/colmap.py).
  * Common inputs (device): the images' observation lists as CSR -- offsets [V+1] int64 ascending, point [offsets[V]] int32 = dense
  *   point index into xyz or -1, in file order (image index = position in images.bin) -- and xyz [P][3] fp64.  An entry outside

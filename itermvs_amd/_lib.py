@@ -199,6 +199,8 @@ PROTOTYPES = {
     "itermvs_fuse_points_workspace_bytes": (C.c_int, [C.c_int32, C.c_int32]),
     "itermvs_fuse_points": (C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                       C.c_int32, C.c_void_p, C.c_void_p]),
+    "itermvs_fuse_points_normals": (C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
+                                              C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "itermvs_view_scores": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p,
                                       C.c_void_p]),
     "itermvs_depth_ranges": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

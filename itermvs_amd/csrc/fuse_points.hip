@@ -9,6 +9,12 @@
 // Ordering comes from the stream alone: no workgroup waits on another, no atomics, so the bytes do not depend on scheduling.
 // Arithmetic: oracle/fusion_oracle.py:unproject_points -- pixel indices as float64, float32 matrices upcast, k-ascending products
 // and sums, each rounded once (-ffp-contract=off), one round-to-nearest conversion to float32 at the end.
+// itermvs_fuse_points_normals: the same three launches with an emit kernel that writes 27-byte records (x, y, z, nx, ny, nz
+// float32, red, green, blue uint8).  Count, scan, the vertex index, the coordinates and the colour are the code of the 15-byte
+// path; the normal is the cross product of depth_avg's camera-space differences along the row and the column, turned towards
+// the camera and rotated to world space (definition: include/itermvs_hip.h; numpy restatement: tests/fuse_normals_reference.py).
+#include <cmath>
+
 #include "common.hpp"
 
 namespace itermvs {
@@ -17,6 +23,7 @@ constexpr int kPtsBlock = 256;                 // pixels per workgroup = 4 waves
 constexpr int kPtsWaves = kPtsBlock / 64;
 constexpr int kScanBlock = 1024;
 constexpr int kRecordBytes = 15;
+constexpr int kNormalRecordBytes = 27;         // x y z | nx ny nz | red green blue
 
 // the same two products as fusion.hip (kept there untouched): (3x3 | rows 0..2 of 4x4, float32 upcast) @ float64 point
 __device__ __forceinline__ void pts_mat3(const float* __restrict__ m, double x, double y, double z, double& ox, double& oy,
@@ -116,15 +123,10 @@ __global__ void __launch_bounds__(kScanBlock) fuse_points_scan_kernel(uint32_t* 
     }
 }
 
-__global__ void __launch_bounds__(kPtsBlock) fuse_points_emit_kernel(const double* __restrict__ depth_avg,
-                                                                     const uint8_t* __restrict__ final_mask,
-                                                                     const float* __restrict__ cam, const uint8_t* __restrict__ rgb,
-                                                                     uint32_t n, uint32_t W, const uint32_t* __restrict__ ws,
-                                                                     const long long* __restrict__ view_row,
-                                                                     uint8_t* __restrict__ records, unsigned long long capacity) {
+// the vertex index of this lane's pixel: the view's first vertex + the workgroups before it (scan) + the waves and lanes before it
+__device__ __forceinline__ unsigned long long pts_vertex_index(bool on, const uint32_t* __restrict__ ws,
+                                                               const long long* __restrict__ view_row) {
     __shared__ uint32_t part[kPtsWaves];
-    const uint32_t p = blockIdx.x * kPtsBlock + threadIdx.x;
-    const bool on = p < n && final_mask[p] != 0;
     uint32_t total;
     const uint32_t rank = wave_rank(on, total);
     const int wv = threadIdx.x >> 6;
@@ -132,20 +134,111 @@ __global__ void __launch_bounds__(kPtsBlock) fuse_points_emit_kernel(const doubl
     __syncthreads();
     uint32_t before = 0;
     for (int k = 0; k < kPtsWaves; ++k) before += k < wv ? part[k] : 0u;
-    const unsigned long long idx = (unsigned long long)view_row[3] + ws[blockIdx.x] + before + rank;
-    if (!on || idx >= capacity) return;                    // the ONLY store below is guarded by idx < capacity
+    return (unsigned long long)view_row[3] + ws[blockIdx.x] + before + rank;
+}
+
+// camera-space point of pixel (x, y) at depth d (eval.py:291-292)
+__device__ __forceinline__ void pts_camera(const float* __restrict__ cam, uint32_t x, uint32_t y, double d, double& rx, double& ry,
+                                           double& rz) {
+    pts_mat3(cam, (double)x * d, (double)y * d, d, rx, ry, rz);
+}
+
+// the records are not padded: no alignment to rely on, byte stores
+__device__ __forceinline__ void pts_put_f32(uint8_t* __restrict__ o, float v) {
+    const uint32_t b = __float_as_uint(v);
+    o[0] = (uint8_t)b; o[1] = (uint8_t)(b >> 8); o[2] = (uint8_t)(b >> 16); o[3] = (uint8_t)(b >> 24);
+}
+
+// the part of a vertex record that both emit kernels write: world coordinates of the camera-space point (eval.py:293-294)
+// -> xyz[0..11], colour of pixel p -> colour[0..2] ((uint8 / 255. * 255).astype(uint8) is the identity)
+__device__ __forceinline__ void pts_put_vertex(const float* __restrict__ cam, double rx, double ry, double rz,
+                                                 const uint8_t* __restrict__ rgb, uint32_t p, uint8_t* __restrict__ xyz,
+                                                 uint8_t* __restrict__ colour) {
+    double wx, wy, wz;
+    pts_mat34(cam + 9, rx, ry, rz, wx, wy, wz);
+    pts_put_f32(xyz, (float)wx); pts_put_f32(xyz + 4, (float)wy); pts_put_f32(xyz + 8, (float)wz);
+    const uint8_t* c = rgb + (size_t)p * 3;
+    colour[0] = c[0]; colour[1] = c[1]; colour[2] = c[2];
+}
+
+__global__ void __launch_bounds__(kPtsBlock) fuse_points_emit_kernel(const double* __restrict__ depth_avg,
+                                                                     const uint8_t* __restrict__ final_mask,
+                                                                     const float* __restrict__ cam, const uint8_t* __restrict__ rgb,
+                                                                     uint32_t n, uint32_t W, const uint32_t* __restrict__ ws,
+                                                                     const long long* __restrict__ view_row,
+                                                                     uint8_t* __restrict__ records, unsigned long long capacity) {
+    const uint32_t p = blockIdx.x * kPtsBlock + threadIdx.x;
+    const bool on = p < n && final_mask[p] != 0;
+    const unsigned long long idx = pts_vertex_index(on, ws, view_row);
+    if (!on || idx >= capacity) return;                    // the ONLY stores below are guarded by idx < capacity
+    const uint32_t y = p / W, x = p - y * W;
+    double rx, ry, rz;
+    pts_camera(cam, x, y, depth_avg[p], rx, ry, rz);
+    uint8_t* o = records + idx * kRecordBytes;
+    pts_put_vertex(cam, rx, ry, rz, rgb, p, o, o + 12);
+}
+
+// the neighbour's depth dq lies on the surface of the pixel at depth d (finite, > 0); a comparison with NaN is false
+__device__ __forceinline__ bool pts_same_surface(double dq, double d, double edge_thres) {
+    return std::isfinite(dq) && dq > 0.0 && fabs(dq - d) < edge_thres * d;
+}
+
+// the tangent along one axis from the camera-space points of the neighbours lo (x-1 | y-1) and hi (x+1 | y+1): hi - lo when both
+// are usable, one-sided against the pixel's own point c when one is, false when neither is.  in_lo / in_hi: inside the image; the
+// depth of a neighbour outside it is never loaded.
+__device__ __forceinline__ bool pts_tangent(const double* __restrict__ depth_avg, const float* __restrict__ cam, bool in_lo,
+                                            uint32_t p_lo, uint32_t x_lo, uint32_t y_lo, bool in_hi, uint32_t p_hi, uint32_t x_hi,
+                                            uint32_t y_hi, double d, double edge_thres, const double (&c)[3], double (&t)[3]) {
+    const double d_lo = in_lo ? depth_avg[p_lo] : 0.0, d_hi = in_hi ? depth_avg[p_hi] : 0.0;      // 0 is never usable
+    const bool lo = pts_same_surface(d_lo, d, edge_thres), hi = pts_same_surface(d_hi, d, edge_thres);
+    if (!lo && !hi) return false;
+    double a[3] = {c[0], c[1], c[2]}, b[3] = {c[0], c[1], c[2]};
+    if (hi) pts_camera(cam, x_hi, y_hi, d_hi, a[0], a[1], a[2]);
+    if (lo) pts_camera(cam, x_lo, y_lo, d_lo, b[0], b[1], b[2]);
+    t[0] = a[0] - b[0]; t[1] = a[1] - b[1]; t[2] = a[2] - b[2];
+    return true;
+}
+
+// the unit normal of pixel p = (x, y) with depth d and camera-space point c, in world space and facing the reference camera;
+// (0, 0, 0) where it is not defined.  p + W < 2^32 by kPtsMaxPixels.
+__device__ __forceinline__ void pts_normal(const double* __restrict__ depth_avg, const float* __restrict__ cam, uint32_t p,
+                                           uint32_t x, uint32_t y, uint32_t W, uint32_t n, double d, double edge_thres,
+                                           const double (&c)[3], float (&out)[3]) {
+    out[0] = out[1] = out[2] = 0.0f;
+    if (!(std::isfinite(d) && d > 0.0)) return;
+    double tx[3], ty[3];
+    if (!pts_tangent(depth_avg, cam, x > 0, p - 1, x - 1, y, x + 1 < W, p + 1, x + 1, y, d, edge_thres, c, tx)) return;
+    if (!pts_tangent(depth_avg, cam, y > 0, p - W, x, y - 1, p + W < n, p + W, x, y + 1, d, edge_thres, c, ty)) return;
+    double nc[3] = {tx[1] * ty[2] - tx[2] * ty[1], tx[2] * ty[0] - tx[0] * ty[2], tx[0] * ty[1] - tx[1] * ty[0]};
+    const double s = (nc[0] * c[0] + nc[1] * c[1]) + nc[2] * c[2];
+    if (s > 0.0) { nc[0] = -nc[0]; nc[1] = -nc[1]; nc[2] = -nc[2]; }       // towards the camera, the origin of camera space
+    const float* r = cam + 9;                                                 // rows 0..2 of inv(E_ref); its 3x3 part rotates
+    const double nx = ((double)r[0] * nc[0] + (double)r[1] * nc[1]) + (double)r[2] * nc[2];
+    const double ny = ((double)r[4] * nc[0] + (double)r[5] * nc[1]) + (double)r[6] * nc[2];
+    const double nz = ((double)r[8] * nc[0] + (double)r[9] * nc[1]) + (double)r[10] * nc[2];
+    const double len = sqrt((nx * nx + ny * ny) + nz * nz);
+    if (!(std::isfinite(len) && len > 0.0)) return;
+    out[0] = (float)(nx / len); out[1] = (float)(ny / len); out[2] = (float)(nz / len);
+}
+
+// fuse_points_emit_kernel with the normal between the coordinates and the colour
+__global__ void __launch_bounds__(kPtsBlock) fuse_points_normals_emit_kernel(
+    const double* __restrict__ depth_avg, const uint8_t* __restrict__ final_mask, const float* __restrict__ cam,
+    const uint8_t* __restrict__ rgb, uint32_t n, uint32_t W, double edge_thres, const uint32_t* __restrict__ ws,
+    const long long* __restrict__ view_row, uint8_t* __restrict__ records, unsigned long long capacity) {
+    const uint32_t p = blockIdx.x * kPtsBlock + threadIdx.x;
+    const bool on = p < n && final_mask[p] != 0;
+    const unsigned long long idx = pts_vertex_index(on, ws, view_row);
+    if (!on || idx >= capacity) return;                    // the ONLY stores below are guarded by idx < capacity
     const uint32_t y = p / W, x = p - y * W;
     const double d = depth_avg[p];
-    double rx, ry, rz, wx, wy, wz;
-    pts_mat3(cam, (double)x * d, (double)y * d, d, rx, ry, rz);        // eval.py:291-292
-    pts_mat34(cam + 9, rx, ry, rz, wx, wy, wz);                        // eval.py:293-294
-    const uint32_t bx = __float_as_uint((float)wx), by = __float_as_uint((float)wy), bz = __float_as_uint((float)wz);
-    const uint8_t* c = rgb + (size_t)p * 3;                             // (uint8 / 255. * 255).astype(uint8) is the identity
-    uint8_t* o = records + idx * kRecordBytes;                          // 15-byte records: no alignment to rely on
-    o[0] = (uint8_t)bx; o[1] = (uint8_t)(bx >> 8); o[2] = (uint8_t)(bx >> 16); o[3] = (uint8_t)(bx >> 24);
-    o[4] = (uint8_t)by; o[5] = (uint8_t)(by >> 8); o[6] = (uint8_t)(by >> 16); o[7] = (uint8_t)(by >> 24);
-    o[8] = (uint8_t)bz; o[9] = (uint8_t)(bz >> 8); o[10] = (uint8_t)(bz >> 16); o[11] = (uint8_t)(bz >> 24);
-    o[12] = c[0]; o[13] = c[1]; o[14] = c[2];
+    double c[3];
+    pts_camera(cam, x, y, d, c[0], c[1], c[2]);
+    float nrm[3];
+    pts_normal(depth_avg, cam, p, x, y, W, n, d, edge_thres, c, nrm);
+    uint8_t* o = records + idx * kNormalRecordBytes;
+    pts_put_vertex(cam, c[0], c[1], c[2], rgb, p, o, o + 24);
+    pts_put_f32(o + 12, nrm[0]); pts_put_f32(o + 16, nrm[1]); pts_put_f32(o + 20, nrm[2]);
 }
 
 // H*W <= this keeps every 32-bit pixel index, workgroup count and relative offset in range
@@ -161,22 +254,57 @@ extern "C" int itermvs_fuse_points_workspace_bytes(int32_t H, int32_t W) {
     return (int)(3 * nblocks * (long long)sizeof(uint32_t));
 }
 
-extern "C" int itermvs_fuse_points(const double* depth_avg, const uint8_t* final_mask, const uint8_t* photo_mask,
-                                   const uint8_t* geo_mask, const float* cam, const uint8_t* rgb, int32_t H, int32_t W,
-                                   uint8_t* records, int64_t capacity, uint64_t* cursor, int64_t* view_counts, int32_t view,
-                                   uint32_t* workspace, void* stream) {
+// the argument checks that both entry points make, in this order, before anything is launched
+static int fuse_points_check(const double* depth_avg, const uint8_t* final_mask, const float* cam, const uint8_t* rgb, int32_t H,
+                             int32_t W, const uint8_t* records, int64_t capacity, const uint64_t* cursor, const int64_t* view_counts,
+                             int32_t view, const uint32_t* workspace) {
     ITERMVS_RETURN_IF(!depth_avg || !final_mask || !cam || !rgb || !cursor || !view_counts || !workspace, ITERMVS_ERR_NULL);
     ITERMVS_RETURN_IF(!records && capacity != 0, ITERMVS_ERR_NULL);
     ITERMVS_RETURN_IF(H < 1 || W < 1 || (long long)H * W > kPtsMaxPixels || capacity < 0 || view < 0, ITERMVS_ERR_DIMS);
-    const uint32_t n = (uint32_t)((long long)H * W);
-    const uint32_t nblocks = (n + kPtsBlock - 1) / kPtsBlock;
+    return ITERMVS_OK;
+}
+
+// the first two launches of both entry points -> the view's row of view_counts, which the emit kernel reads
+static const long long* fuse_points_count_and_scan(const uint8_t* final_mask, const uint8_t* photo_mask, const uint8_t* geo_mask,
+                                                   uint32_t n, uint32_t nblocks, uint64_t* cursor, int64_t* view_counts,
+                                                   int32_t view, uint32_t* workspace, hipStream_t s) {
     long long* row = (long long*)view_counts + (size_t)view * 4;
-    hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(fuse_points_count_kernel, dim3(nblocks), dim3(kPtsBlock), 0, s, final_mask, photo_mask, geo_mask, n,
                        workspace);
     hipLaunchKernelGGL(fuse_points_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, workspace, nblocks, photo_mask ? 1 : 0,
                        geo_mask ? 1 : 0, (unsigned long long*)cursor, row);
+    return row;
+}
+
+extern "C" int itermvs_fuse_points(const double* depth_avg, const uint8_t* final_mask, const uint8_t* photo_mask,
+                                   const uint8_t* geo_mask, const float* cam, const uint8_t* rgb, int32_t H, int32_t W,
+                                   uint8_t* records, int64_t capacity, uint64_t* cursor, int64_t* view_counts, int32_t view,
+                                   uint32_t* workspace, void* stream) {
+    const int bad = fuse_points_check(depth_avg, final_mask, cam, rgb, H, W, records, capacity, cursor, view_counts, view, workspace);
+    if (bad != ITERMVS_OK) return bad;
+    const uint32_t n = (uint32_t)((long long)H * W);
+    const uint32_t nblocks = (n + kPtsBlock - 1) / kPtsBlock;
+    hipStream_t s = (hipStream_t)stream;
+    const long long* row = fuse_points_count_and_scan(final_mask, photo_mask, geo_mask, n, nblocks, cursor, view_counts, view,
+                                                      workspace, s);
     hipLaunchKernelGGL(fuse_points_emit_kernel, dim3(nblocks), dim3(kPtsBlock), 0, s, depth_avg, final_mask, cam, rgb, n,
-                       (uint32_t)W, workspace, (const long long*)row, records, (unsigned long long)capacity);
+                       (uint32_t)W, workspace, row, records, (unsigned long long)capacity);
+    return itermvs_launch_status();
+}
+
+extern "C" int itermvs_fuse_points_normals(const double* depth_avg, const uint8_t* final_mask, const uint8_t* photo_mask,
+                                           const uint8_t* geo_mask, const float* cam, const uint8_t* rgb, int32_t H, int32_t W,
+                                           double edge_thres, uint8_t* records, int64_t capacity, uint64_t* cursor,
+                                           int64_t* view_counts, int32_t view, uint32_t* workspace, void* stream) {
+    const int bad = fuse_points_check(depth_avg, final_mask, cam, rgb, H, W, records, capacity, cursor, view_counts, view, workspace);
+    if (bad != ITERMVS_OK) return bad;
+    ITERMVS_RETURN_IF(!std::isfinite(edge_thres) || !(edge_thres > 0.0), ITERMVS_ERR_DIMS);
+    const uint32_t n = (uint32_t)((long long)H * W);
+    const uint32_t nblocks = (n + kPtsBlock - 1) / kPtsBlock;
+    hipStream_t s = (hipStream_t)stream;
+    const long long* row = fuse_points_count_and_scan(final_mask, photo_mask, geo_mask, n, nblocks, cursor, view_counts, view,
+                                                      workspace, s);
+    hipLaunchKernelGGL(fuse_points_normals_emit_kernel, dim3(nblocks), dim3(kPtsBlock), 0, s, depth_avg, final_mask, cam, rgb, n,
+                       (uint32_t)W, edge_thres, workspace, row, records, (unsigned long long)capacity);
     return itermvs_launch_status();
 }

@@ -60,10 +60,12 @@ def fuse_reference_view(depth_ref, conf_ref, k_ref, e_ref, src_depths: Sequence,
                           geo_pixel_thres, geo_depth_thres, photo_thres, geo_mask_thres)
 
 
-def ply_header(n: int) -> bytes:
-    """the header of the binary little-endian PLY with ``n`` vertices of eval.py:298-308"""
+def ply_header(n: int, normals: bool = False) -> bytes:
+    """the header of the binary little-endian PLY with ``n`` vertices of eval.py:298-308; ``normals``: with nx, ny, nz between
+    z and red, the property order of COLMAP's fused.ply"""
     return ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
-            "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % n).encode("ascii")
+            "%sproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n"
+            % (n, "property float nx\nproperty float ny\nproperty float nz\n" if normals else "")).encode("ascii")
 
 
 def write_ply(filename: str, xyz: np.ndarray, rgb: np.ndarray) -> None:
@@ -107,10 +109,10 @@ def _save_view_masks(mask_folder: str, view: int, photo, geo, final) -> None:
         save_mask(os.path.join(mask_folder, "{:0>8}_{}.png".format(view, name)), m.cpu().numpy() if torch.is_tensor(m) else m)
 
 
-def group_views(n_views: int, h: int, w: int, budget_bytes: int) -> List[Tuple[int, int]]:
+def group_views(n_views: int, h: int, w: int, budget_bytes: int, record_bytes: int = ops.POINT_RECORD_BYTES) -> List[Tuple[int, int]]:
     """consecutive [start, stop) ranges of reference views whose worst case (every pixel of every view survives:
-    views * h * w * 15 bytes) fits ``budget_bytes``; a budget below one view cannot be met"""
-    per_view = h * w * ops.POINT_RECORD_BYTES
+    views * h * w * record_bytes, 15 bytes per vertex unless given) fits ``budget_bytes``; a budget below one view cannot be met"""
+    per_view = h * w * record_bytes
     k = int(budget_bytes) // per_view
     if k < 1:
         raise ValueError(f"records budget of {budget_bytes} bytes is below one {w}x{h} view ({per_view} bytes)")
@@ -162,7 +164,8 @@ def _download(records: torch.Tensor, nbytes: int, write, seconds: Dict[str, floa
 def fuse_scan(pairs: Sequence[Tuple[int, Sequence[int]]], cams, depths, confidences, images, plyfilename: str,
               geo_pixel_thres: float, geo_depth_thres: float, photo_thres: float, geo_mask_thres: int = 3, device: str = "cuda",
               records_budget: int = 2 << 30, mask_folder: str = None, group_capacity: int = None,
-              info: dict = None, dedupe: bool = False) -> Dict[int, Tuple[float, float, float]]:
+              info: dict = None, dedupe: bool = False, normals: bool = False,
+              normal_edge_thres: float = 0.01) -> Dict[int, Tuple[float, float, float]]:
     """eval.py:215-309 for a scan that is already in memory, with the point cloud assembled on the GPU: per reference view one
     ``itermvs_fuse_depth`` and one ``itermvs_fuse_points``, enqueued back to back; the host synchronises once per GROUP of
     reference views, downloads the group's finished vertex records and appends them to the PLY.
@@ -177,12 +180,18 @@ def fuse_scan(pairs: Sequence[Tuple[int, Sequence[int]]], cams, depths, confiden
     uint8 [H,W] claim map per view lives on the GPU for the whole scan, across the flush groups; a pixel that an emitted point of an
     earlier reference view was verified against is left out of ``final``.  The vertices are a sub-sequence of the ones without
     it.  The final mask share of the result and the final masks of ``mask_folder`` are those of the emit mask.
+    normals: every vertex carries nx, ny, nz (``itermvs_fuse_points_normals`` in place of ``itermvs_fuse_points``, 27-byte records,
+    the header of ``ply_header(n, normals=True)``): the unit normal of the averaged depth map's surface at the pixel, facing the
+    reference camera; ``normal_edge_thres``: relative depth step beyond which a neighbouring pixel is not used for it.  The
+    vertices, their order and every other byte are those without it.
     -> {ref_view: (geo, photo, final mask share)} like ``filter_depth``."""
     dev = torch.device(device)
     clock = time.perf_counter
     seconds = {"upload": 0.0, "enqueue": 0.0, "gpu_wait": 0.0, "download_wait": 0.0, "file_write": 0.0, "mask_write": 0.0}
     n_sync = n_chunks = 0
-    rec = ops.POINT_RECORD_BYTES
+    rec = ops.POINT_NORMAL_RECORD_BYTES if normals else ops.POINT_RECORD_BYTES
+    emit = ops.fuse_points_normals if normals else ops.fuse_points
+    emit_options = {"edge_thres": normal_edge_thres} if normals else {}
     with torch.cuda.device(dev):
         t0 = clock()
         as_t = lambda a, dt: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dev, dt).contiguous()  # noqa: E731
@@ -207,7 +216,7 @@ def fuse_scan(pairs: Sequence[Tuple[int, Sequence[int]]], cams, depths, confiden
         first_mat = np.cumsum([0] + [len(m) for m in mats])
         mats = torch.from_numpy(np.concatenate(mats)).to(dev) if pairs else None
         cam = torch.from_numpy(np.stack(cam).astype(np.float32)).to(dev) if pairs else None
-        groups = group_views(len(pairs), h, w, records_budget)
+        groups = group_views(len(pairs), h, w, records_budget, rec)
         capacity = max((b - a) * h * w for a, b in groups) if group_capacity is None and groups else int(group_capacity or 0)
         records = torch.empty(capacity * rec, device=dev, dtype=torch.uint8)
         cursor = torch.zeros(1, device=dev, dtype=torch.int64)
@@ -231,7 +240,7 @@ def fuse_scan(pairs: Sequence[Tuple[int, Sequence[int]]], cams, depths, confiden
                         avg, photo, geo, final, _ = ops.fuse_depth_claim(*maps, claimed[ref], [claimed[v] for v in srcs], *thres)
                     else:
                         avg, photo, geo, final, _ = ops.fuse_depth(*maps, *thres)
-                    ops.fuse_points(avg, final, cam[i], rgb[i], records, cursor, counts, i, photo, geo, capacity, workspace)
+                    emit(avg, final, cam[i], rgb[i], records, cursor, counts, i, photo, geo, capacity, workspace, **emit_options)
                     if mask_folder is not None:
                         masks.append((ref, photo, geo, final))
                 host[a:b].copy_(counts[a:b], non_blocking=True)
@@ -252,7 +261,7 @@ def fuse_scan(pairs: Sequence[Tuple[int, Sequence[int]]], cams, depths, confiden
                 n_vertices += n
                 if b == len(pairs):                                    # the total is known: header, earlier groups, then stream
                     t3 = clock()
-                    f.write(ply_header(n_vertices))
+                    f.write(ply_header(n_vertices, normals))
                     for part in spooled:
                         f.write(part)
                     seconds["file_write"] += clock() - t3
@@ -264,10 +273,11 @@ def fuse_scan(pairs: Sequence[Tuple[int, Sequence[int]]], cams, depths, confiden
                     _save_view_masks(mask_folder, ref, photo, geo, final)
                 seconds["mask_write"] += clock() - t3
             if not groups:
-                f.write(ply_header(0))
+                f.write(ply_header(0, normals))
     if info is not None:
         info.update(groups=groups, synchronisations=n_sync, downloads=len(groups), download_chunks=n_chunks,
-                    vertices=n_vertices, capacity=capacity, seconds=seconds, dedupe=bool(dedupe))
+                    vertices=n_vertices, capacity=capacity, seconds=seconds, dedupe=bool(dedupe),
+                    normals=bool(normals), record_bytes=rec)
     return stats
 
 
@@ -275,7 +285,7 @@ def filter_depth(scan_folder: str, out_folder: str, plyfilename: str, geo_pixel_
                  photo_thres: float, images: Dict[int, np.ndarray] = None, intrinsics_scale: Tuple[float, float] = None,
                  geo_mask_thres: int = 3, device: str = "cuda", img_wh: Tuple[int, int] = None, points: str = "host",
                  save_masks: bool = False, records_budget: int = 2 << 30, info: dict = None,
-                 dedupe: bool = False) -> Dict[str, float]:
+                 dedupe: bool = False, normals: bool = False, normal_edge_thres: float = 0.01) -> Dict[str, float]:
     """eval.py:215-309: for every reference view of ``pair.txt`` fuse its depth map with its source views' and append the
     surviving pixels to one point cloud.
 
@@ -291,12 +301,16 @@ def filter_depth(scan_folder: str, out_folder: str, plyfilename: str, geo_pixel_
     host synchronises once per group of reference views (``records_budget`` bytes of records per group; ``info`` as in
     ``fuse_scan``); same header, vertex order and colours, coordinates equal up to the last float64 bit of ``np.matmul``.
     ``save_masks``: also write ``<out_folder>/mask/{view:0>8}_photo.png``, ``_geo.png``, ``_final.png`` (eval.py:266-269).
-    ``dedupe``: ``fuse_scan``'s, so it needs ``points="device"``."""
+    ``dedupe``: ``fuse_scan``'s, so it needs ``points="device"``.  ``normals``, ``normal_edge_thres``: ``fuse_scan``'s, with the
+    same need."""
     if points not in ("host", "device"):
         raise ValueError(f"filter_depth: points must be 'host' or 'device', got {points!r}")
     if dedupe and points != "device":
         raise ValueError("filter_depth: dedupe=True needs points='device' (the claim maps live on the GPU between the reference "
                          f"views), got points={points!r}")
+    if normals and points != "device":
+        raise ValueError("filter_depth: normals=True needs points='device' (the normals are computed from the fused depth map on "
+                         f"the GPU while the vertices are emitted), got points={points!r}")
     pairs = read_pair_file(os.path.join(scan_folder, "pair.txt"))
     mask_folder = os.path.join(out_folder, "mask") if save_masks else None
     if img_wh is None and images is None and intrinsics_scale is None:
@@ -352,7 +366,8 @@ def filter_depth(scan_folder: str, out_folder: str, plyfilename: str, geo_pixel_
             else:
                 rgb[ref_view] = pixels.pop(ref_view) if ref_view in pixels else np.full((h, w, 3), 127, np.uint8)
         return fuse_scan(pairs, cams, depths, confs, rgb, plyfilename, geo_pixel_thres, geo_depth_thres, photo_thres,
-                         geo_mask_thres, device, records_budget, mask_folder, info=info, dedupe=dedupe)
+                         geo_mask_thres, device, records_budget, mask_folder, info=info, dedupe=dedupe, normals=normals,
+                         normal_edge_thres=normal_edge_thres)
 
     vertexs, colors, stats = [], [], {}
     for ref_view, src_views in pairs:

@@ -1366,6 +1366,40 @@ def fuse_points_workspace_bytes(h: int, w: int) -> int:
     return n
 
 
+def _fuse_points(what: str, record_bytes: int, depth_avg: Tensor, final_mask: Tensor, cam: Tensor, rgb: Tensor, records: Tensor,
+                 cursor: Tensor, view_counts: Tensor, view: int, photo_mask: Optional[Tensor], geo_mask: Optional[Tensor],
+                 capacity: Optional[int], workspace: Optional[Tensor], extra: tuple = ()) -> None:
+    """the checks and the call of fuse_points / fuse_points_normals; ``extra``: the entry point's arguments between W and records"""
+    h, w = depth_avg.shape
+    want = ((depth_avg, torch.float64, (h, w)), (final_mask, torch.uint8, (h, w)), (cam, torch.float32, (21,)),
+            (rgb, torch.uint8, (h, w, 3)), (cursor, torch.int64, (1,)))
+    masks = [m for m in (photo_mask, geo_mask) if m is not None]
+    for t, dt, shp in want + tuple((m, torch.uint8, (h, w)) for m in masks):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{what}: expected CUDA/ROCm tensors - the IterMVS HIP engine has no CPU path")
+        if t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous():
+            raise RuntimeError(f"{what}: expected a contiguous {dt} tensor of shape {shp}, got {t.dtype} {tuple(t.shape)}")
+    for t, dt, name in ((records, torch.uint8, "records"), (view_counts, torch.int64, "view_counts")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise RuntimeError(f"{what}: {name} must be a contiguous {dt} CUDA/ROCm tensor")
+    if view_counts.dim() != 2 or view_counts.shape[1] != 4 or not 0 <= view < view_counts.shape[0]:
+        raise RuntimeError(f"{what}: view_counts must be [n_views,4] with view {view} inside it")
+    cap = records.numel() // record_bytes if capacity is None else int(capacity)
+    if cap < 0 or cap * record_bytes > records.numel():
+        raise RuntimeError(f"{what}: capacity {cap} vertices does not fit records ({records.numel()} bytes)")
+    need = fuse_points_workspace_bytes(h, w)
+    if workspace is None:
+        workspace = torch.empty(need, device=depth_avg.device, dtype=torch.uint8)
+    elif not workspace.is_cuda or workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous():
+        raise RuntimeError(f"{what}: workspace must be a contiguous uint8 CUDA/ROCm tensor of >= {need} bytes")
+    ptr = lambda m: None if m is None else m.data_ptr()    # noqa: E731
+    check(getattr(_lib.load(), "itermvs_" + what)(depth_avg.data_ptr(), final_mask.data_ptr(), ptr(photo_mask), ptr(geo_mask),
+                                                  cam.data_ptr(), rgb.data_ptr(), h, w, *extra, records.data_ptr() if cap else None,
+                                                  cap, cursor.data_ptr(), view_counts.data_ptr(), int(view), workspace.data_ptr(),
+                                                  _stream()),
+          "itermvs_" + what)
+
+
 def fuse_points(depth_avg: Tensor, final_mask: Tensor, cam: Tensor, rgb: Tensor, records: Tensor, cursor: Tensor,
                 view_counts: Tensor, view: int, photo_mask: Optional[Tensor] = None, geo_mask: Optional[Tensor] = None,
                 capacity: Optional[int] = None, workspace: Optional[Tensor] = None) -> None:
@@ -1374,33 +1408,22 @@ def fuse_points(depth_avg: Tensor, final_mask: Tensor, cam: Tensor, rgb: Tensor,
     [n,4]: photo, geo, final pixels, first vertex); nothing is read back and nothing synchronises.  depth_avg float64 [H,W],
     masks uint8 [H,W], cam float32 [21] = inv(K) | inv(E)[:3], rgb uint8 [H,W,3].  ``capacity`` (vertices) defaults to all of
     ``records``; ``workspace``: uint8 scratch of fuse_points_workspace_bytes(H, W), allocated here when not given."""
-    h, w = depth_avg.shape
-    want = ((depth_avg, torch.float64, (h, w)), (final_mask, torch.uint8, (h, w)), (cam, torch.float32, (21,)),
-            (rgb, torch.uint8, (h, w, 3)), (cursor, torch.int64, (1,)))
-    masks = [m for m in (photo_mask, geo_mask) if m is not None]
-    for t, dt, shp in want + tuple((m, torch.uint8, (h, w)) for m in masks):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise RuntimeError("fuse_points: expected CUDA/ROCm tensors - the IterMVS HIP engine has no CPU path")
-        if t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous():
-            raise RuntimeError(f"fuse_points: expected a contiguous {dt} tensor of shape {shp}, got {t.dtype} {tuple(t.shape)}")
-    for t, dt, name in ((records, torch.uint8, "records"), (view_counts, torch.int64, "view_counts")):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or not t.is_contiguous():
-            raise RuntimeError(f"fuse_points: {name} must be a contiguous {dt} CUDA/ROCm tensor")
-    if view_counts.dim() != 2 or view_counts.shape[1] != 4 or not 0 <= view < view_counts.shape[0]:
-        raise RuntimeError(f"fuse_points: view_counts must be [n_views,4] with view {view} inside it")
-    cap = records.numel() // POINT_RECORD_BYTES if capacity is None else int(capacity)
-    if cap < 0 or cap * POINT_RECORD_BYTES > records.numel():
-        raise RuntimeError(f"fuse_points: capacity {cap} vertices does not fit records ({records.numel()} bytes)")
-    need = fuse_points_workspace_bytes(h, w)
-    if workspace is None:
-        workspace = torch.empty(need, device=depth_avg.device, dtype=torch.uint8)
-    elif not workspace.is_cuda or workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous():
-        raise RuntimeError(f"fuse_points: workspace must be a contiguous uint8 CUDA/ROCm tensor of >= {need} bytes")
-    ptr = lambda m: None if m is None else m.data_ptr()    # noqa: E731
-    check(_lib.load().itermvs_fuse_points(depth_avg.data_ptr(), final_mask.data_ptr(), ptr(photo_mask), ptr(geo_mask),
-                                          cam.data_ptr(), rgb.data_ptr(), h, w, records.data_ptr() if cap else None, cap,
-                                          cursor.data_ptr(), view_counts.data_ptr(), int(view), workspace.data_ptr(), _stream()),
-          "itermvs_fuse_points")
+    _fuse_points("fuse_points", POINT_RECORD_BYTES, depth_avg, final_mask, cam, rgb, records, cursor, view_counts, view,
+                 photo_mask, geo_mask, capacity, workspace)
+
+
+POINT_NORMAL_RECORD_BYTES = 27      # x, y, z, nx, ny, nz float32, red, green, blue uint8 (the vertex of COLMAP's fused.ply)
+
+
+def fuse_points_normals(depth_avg: Tensor, final_mask: Tensor, cam: Tensor, rgb: Tensor, records: Tensor, cursor: Tensor,
+                        view_counts: Tensor, view: int, photo_mask: Optional[Tensor] = None, geo_mask: Optional[Tensor] = None,
+                        capacity: Optional[int] = None, workspace: Optional[Tensor] = None, edge_thres: float = 0.01) -> None:
+    """itermvs_fuse_points_normals: ``fuse_points`` with 27-byte records that carry, between the coordinates and the colour, the
+    unit normal of the surface at the pixel in world space, facing the reference camera: the cross product of ``depth_avg``'s
+    camera-space differences along the row and the column, where a neighbour whose depth differs by ``edge_thres * depth`` or
+    more is left out (include/itermvs_hip.h has every step); (0, 0, 0) where it is not defined.  Everything else as there."""
+    _fuse_points("fuse_points_normals", POINT_NORMAL_RECORD_BYTES, depth_avg, final_mask, cam, rgb, records, cursor, view_counts,
+                 view, photo_mask, geo_mask, capacity, workspace, extra=(float(edge_thres),))
 
 
 def _colmap_inputs(what: str, offsets: Tensor, point: Tensor, xyz: Tensor, per_view: Tensor, width: int) -> Tuple[int, int]:

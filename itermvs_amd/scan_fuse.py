@@ -247,7 +247,9 @@ def fuse_scans_from_memory(args, dataset, scans: Sequence[str], model, dev) -> D
             stats[scan] = fusion.fuse_scan(pairs, cams, store.depth, store.conf, store.rgb,
                                            os.path.join(args.outdir, scan + ".ply"), args.geo_pixel_thres, args.geo_depth_thres,
                                            args.photo_thres, args.geo_mask_thres, str(dev), mask_folder=mask_folder,
-                                           dedupe=bool(getattr(args, "fuse_dedupe", False)))
+                                           dedupe=bool(getattr(args, "fuse_dedupe", False)),
+                                           normals=bool(getattr(args, "ply_normals", False)),
+                                           normal_edge_thres=float(getattr(args, "normal_edge_thres", 0.01)))
             for v, (g, ph, f) in stats[scan].items():
                 print("processing {}, ref-view{:0>2}, geo_mask:{:3f} photo_mask:{:3f} final_mask: {:3f}".format(scan, v, g, ph, f))
             del store
