@@ -33,7 +33,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define ITERMVS_ABI_VERSION 19
+#define ITERMVS_ABI_VERSION 20
 #define ITERMVS_MAX_SRC 16     /* source views per reference view (pair.txt holds 10) */
 #define ITERMVS_MAX_HYP 8      /* hypotheses per level in the iteration branch (4,4,2) */
 #define ITERMVS_GROUPS 8       /* models/itermvs.py:28  */
@@ -593,6 +593,31 @@ typedef struct itermvs_conv_plan {
 } itermvs_conv_plan;
 
 int itermvs_conv2d_plan(const itermvs_conv_params* p, itermvs_conv_plan* plan);
+
+/* ------------------------------------------------------------------------------------------
+ * itermvs_persistent_plan / itermvs_tile_walk_owner -- diagnostics (ABI 20): the grid rule and the tile walks of the persistent
+ * kernels (csrc/tile_walk.hpp; DESIGN.md lists which kernel uses which), run on the host.  Neither makes a device call.
+ *   itermvs_persistent_plan: the launch of `tiles` tiles (1 .. 2^31 - 1, else ITERMVS_ERR_DIMS) by at most `resident` workgroups:
+ *     grid = min(tiles, resident), rounded down to a multiple of 8 from 16 on when `round8`; whether the XCD-banded tile order
+ *     applies; for ITERMVS_WALK_RUNS the split of the tile list into runs.  STRIDED_LEAD: `grid` counts the tile workgroups only.
+ *   itermvs_tile_walk_owner: runs the kernels' own walk for every workgroup of `plan` (`lead` extra workgroups in front for
+ *     ITERMVS_WALK_STRIDED_LEAD, else 0) and writes, per tile, owner[t] = the workgroup that visits it (STRIDED_LEAD: counted from
+ *     the first tile workgroup; -1: none) and order[t] = its position in that workgroup's sequence.  Returns the number of
+ *     visits to an already visited tile (0 for a correct walk), or a negative status.
+ * ------------------------------------------------------------------------------------------ */
+typedef enum itermvs_walk_kind {
+    ITERMVS_WALK_STRIDED = 0,       /* conv_tile, conv_tile3, res_chain16, lat_conv: tiles w, w + wstep, ... of the list or of an eighth */
+    ITERMVS_WALK_RUNS = 1,          /* gru_conv, down_conv: one run of consecutive tiles per workgroup */
+    ITERMVS_WALK_PLAIN = 2,         /* stack2, head_coop: tiles b, b + grid, ... */
+    ITERMVS_WALK_STRIDED_LEAD = 3   /* stem: STRIDED behind `lead` workgroups that do other work, banded from 8 tile workgroups on */
+} itermvs_walk_kind;
+
+typedef struct itermvs_persistent_plan_t {
+    int32_t grid, banded, run, run_extra;
+} itermvs_persistent_plan_t;
+
+int itermvs_persistent_plan(int64_t tiles, int32_t resident, int32_t round8, int32_t kind, itermvs_persistent_plan_t* out);
+int itermvs_tile_walk_owner(const itermvs_persistent_plan_t* plan, int64_t tiles, int32_t kind, int32_t lead, int32_t* owner, int32_t* order);
 
 /* ------------------------------------------------------------------------------------------
  * itermvs_corrnet -- the whole CorrNet (models/itermvs.py:352-381: conv0..conv2, the two transposed convolutions with

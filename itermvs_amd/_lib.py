@@ -15,7 +15,7 @@ MAX_HYP = 8
 GROUPS = 8
 F32, F16, BF16 = 0, 1, 2      # itermvs_dtype: storage type of feature maps
 GT_DTU, GT_BLENDEDMVS = 0, 1  # itermvs_gt_pyramid recipes
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libitermvs_hip.so")
@@ -97,6 +97,11 @@ class ConvPlan(C.Structure):
         return f"{self.BACKENDS[self.backend]} " + " ".join(shown)
 
 
+class PersistentPlan(C.Structure):
+    """itermvs_persistent_plan_t"""
+    _fields_ = [(n, C.c_int32) for n in ("grid", "banded", "run", "run_extra")]
+
+
 # name -> (restype, argtypes); every symbol include/itermvs_hip.h declares
 PROTOTYPES = {
     "itermvs_version": (C.c_int, []),
@@ -156,6 +161,8 @@ PROTOTYPES = {
                                       C.c_void_p]),
     "itermvs_conv2d": (C.c_int, [C.POINTER(ConvParams), C.c_void_p]),
     "itermvs_conv2d_plan": (C.c_int, [C.POINTER(ConvParams), C.POINTER(ConvPlan)]),
+    "itermvs_persistent_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PersistentPlan)]),
+    "itermvs_tile_walk_owner": (C.c_int, [C.POINTER(PersistentPlan), C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "itermvs_corrnet": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
                                   C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "itermvs_corrnet_bf16x3": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,

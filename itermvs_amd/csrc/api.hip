@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "tile_walk.hpp"
 
 extern "C" int itermvs_version(void) { return ITERMVS_ABI_VERSION; }
 
@@ -21,6 +22,45 @@ extern "C" const char* itermvs_error_string(int status) {
         case ITERMVS_ERR_MODEL: return "camera model not supported (FOV, THIN_PRISM_FISHEYE or an unknown model id)";
         default: return "unknown itermvs status";
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The persistent kernels' grid rule and tile walks on the host (tile_walk.hpp; tests/test_tile_walk_cpu.py)
+// ---------------------------------------------------------------------------------------------
+static bool walk_kind_ok(int32_t kind) { return kind >= ITERMVS_WALK_STRIDED && kind <= ITERMVS_WALK_STRIDED_LEAD; }
+
+extern "C" int itermvs_persistent_plan(int64_t tiles, int32_t resident, int32_t round8, int32_t kind, itermvs_persistent_plan_t* out) {
+    ITERMVS_RETURN_IF(!out, ITERMVS_ERR_NULL);
+    ITERMVS_RETURN_IF(!walk_kind_ok(kind), ITERMVS_ERR_DIMS);
+    return itermvs::persistent_plan(tiles, resident, round8 != 0, (itermvs_walk_kind)kind, out);
+}
+
+extern "C" int itermvs_tile_walk_owner(const itermvs_persistent_plan_t* plan, int64_t tiles, int32_t kind, int32_t lead, int32_t* owner,
+                                       int32_t* order) {
+    using namespace itermvs;
+    ITERMVS_RETURN_IF(!plan || !owner || !order, ITERMVS_ERR_NULL);
+    ITERMVS_RETURN_IF(!walk_kind_ok(kind) || tiles < 1 || tiles >= ((int64_t)1 << 31) || plan->grid < 1 || lead < 0, ITERMVS_ERR_DIMS);
+    ITERMVS_RETURN_IF(kind != ITERMVS_WALK_STRIDED_LEAD && lead != 0, ITERMVS_ERR_DIMS);
+    const int total = (int)tiles, nblocks = plan->grid + lead;
+    for (int t = 0; t < total; ++t) owner[t] = -1;
+    int repeats = 0;
+    auto visit = [&](int b, int t, int pos) {
+        if (t < 0 || t >= total) return;           // (outside the list: shows as an unvisited tile)
+        if (owner[t] >= 0) ++repeats;
+        owner[t] = b - lead;
+        order[t] = pos;
+    };
+    for (int b = lead; b < nblocks; ++b) {
+        if (kind == ITERMVS_WALK_RUNS) {
+            const TileRun r = tile_walk_run(plan->run, plan->run_extra, b, nblocks, plan->banded != 0);
+            for (int i = 0; i < r.count; ++i) visit(b, r.t0 + i, i);
+        } else {
+            const TileWalk k = tile_walk_strided(total, b, nblocks, lead, plan->banded != 0);
+            int pos = 0;
+            for (int64_t w = k.w; w < k.wend && k.wstep > 0; w += k.wstep) visit(b, (int)w, pos++);
+        }
+    }
+    return repeats;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -4,6 +4,7 @@
 
 #include "common.hpp"
 #include "conv_plan.hpp"
+#include "tile_walk.hpp"
 
 namespace itermvs {
 
@@ -15,7 +16,7 @@ struct TileArgs : ConvArgsBase {
     int split, act_b;
     int pad, act, add_mode, out_nhwc, nchunk, nstage, tiles_x, tiles_y, ncb, total;
     uint32_t rcp_tiles_x, rcp_tiles_y;   // floor(2^32 / d) + 1
-    int banded;                          // XCD-banded tile order (see the kernels)
+    int banded;                          // XCD-banded tile order (tile_walk.hpp)
 };
 static_assert(sizeof(TileArgs) == 264, "kernel argument layout");
 
@@ -34,27 +35,25 @@ static inline void fill_tile_args(TileArgs& a, const ConvArgsBase& base, const i
 
 // Persistent grid of conv_tile_kernel / conv_tile3_kernel: about `persist` (ITERMVS_TILE_PERSIST, default 4; measured 630 / 645 /
 // 650 / 648 depth-maps/s at 2 / 3 / 4 / 8, bounded by what fits a CU) workgroups per CU in total, each walking the tile list of
-// its channel block (one tile each when there are fewer tiles than that); never more than are resident at once -- a persistent
-// workgroup queued behind another would serialise its tile list.  Returns the workgroup columns; *banded: the XCD-banded tile
-// order applies.
+// its channel block (one tile each when there are fewer tiles than that); never more than are resident at once.  The resident cap
+// comes from the occupancy query; the workgroup columns and the tile order from persistent_plan (tile_walk.hpp).
 template <class Kernel>
-static inline int persistent_grid(Kernel kern, int block, int lds, int ncb, int total, int persist, int* banded) {
+static inline int persistent_grid(Kernel kern, int block, int lds, int ncb, int total, int persist, PersistentPlan* plan) {
     int fit = 1;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, kern, block, lds) != hipSuccess || fit < 1) fit = 1;
-    int gx = itermvs_num_cus() * (persist < fit ? persist : fit) / ncb;
-    if (gx > total) gx = total;
-    if (gx < 1) gx = 1;
-    if (gx >= 16) gx &= ~7;              // a multiple of 8 workgroup columns: the XCD-banded tile order needs it (85 -> 80 costs nothing)
-    *banded = gx % 8 == 0 && total >= gx ? 1 : 0;
-    return gx;
+    const int resident = itermvs_num_cus() * (persist < fit ? persist : fit) / ncb;
+    return persistent_plan(total, resident < 1 ? 1 : resident, true, ITERMVS_WALK_STRIDED, plan);
 }
 
 struct TileLaunch { TileArgs a; const itermvs_conv_plan& pl; int persist; hipStream_t stream; };
 
 template <class Kernel>
 static inline int launch_persistent(Kernel kern, TileLaunch& t) {
-    const int gx = persistent_grid(kern, 256, t.pl.lds_bytes, t.a.ncb, t.a.total, t.persist, &t.a.banded);
-    hipLaunchKernelGGL(kern, dim3(gx, t.a.ncb), dim3(256), t.pl.lds_bytes, t.stream, t.a);
+    PersistentPlan plan;
+    const int rc = persistent_grid(kern, 256, t.pl.lds_bytes, t.a.ncb, t.a.total, t.persist, &plan);
+    if (rc != ITERMVS_OK) return rc;
+    t.a.banded = plan.banded;
+    hipLaunchKernelGGL(kern, dim3(plan.grid, t.a.ncb), dim3(256), t.pl.lds_bytes, t.stream, t.a);
     return itermvs_launch_status();
 }
 

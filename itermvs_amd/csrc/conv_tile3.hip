@@ -194,8 +194,9 @@ __global__ void __launch_bounds__(256) conv_tile3_kernel(const TileArgs a) {
     const char* __restrict__ abase3 = abase + (second ? 0 : 2 * WPL);                             // A3 = [wl | wh]
     const int P = a.Hout * a.Wout;
 
-    // Tile order (a.banded): workgroup column x runs on XCD x % 8 (round-robin dispatch, gridDim.x a multiple of 8); the tiles of
-    // one XCD are a contiguous run of the tile list (whole image bands), so that tiles sharing halo rows meet in the same 4 MB L2
+    // Tile order: tile_walk_strided (tile_walk.hpp) at lead 0 and a grid that is a multiple of 8 when banded, WRITTEN OUT -- this
+    // kernel sits at its register limit and the inlined call moved its allocation.  Keep it identical to that function by hand; the
+    // CPU test runs the function, not this copy.  No early return: every workgroup column owns a tile (persistent_plan)
     int w = blockIdx.x, wstep = gridDim.x, wend = a.total;
     if (a.banded) {
         const int xcd = blockIdx.x & 7;

@@ -17,6 +17,7 @@
 // 68 vs 55 us: a vector FMA needs a fresh weight operand per 128 multiply-adds and neither the scalar cache nor LDS
 // broadcasts deliver that; the matrix core reuses each operand register 16 times.)
 #include "common.hpp"
+#include "tile_walk.hpp"
 
 namespace itermvs {
 
@@ -740,15 +741,9 @@ static int launch_corrnet(const float* x, int64_t x_sn, const float* const* weig
     a.out = out; a.out2 = out2; a.out_sn = out_sn; a.out2_sn = out2_sn;
     a.vec4 = (((uintptr_t)x) % 16 == 0 && x_sn % 4 == 0) ? 1 : 0;
     a.M = M; a.H = H; a.W = W; a.tiles_x = (W + kCnTile - 1) / kCnTile;
-    static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(corrnet_kernel<false>),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, kCnLdsFloats * 4) == hipSuccess &&
-                                hipFuncSetAttribute(reinterpret_cast<const void*>(corrnet_kernel<true>),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, kCnLdsFloats * 4) == hipSuccess;
-    ITERMVS_RETURN_IF(!attr_ok, ITERMVS_ERR_LAUNCH);
     const dim3 grid(a.tiles_x * ((H + kCnTile - 1) / kCnTile), M);
-    if (split3) hipLaunchKernelGGL(corrnet_kernel<true>, grid, dim3(kCnThreads), kCnLdsFloats * 4, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(corrnet_kernel<false>, grid, dim3(kCnThreads), kCnLdsFloats * 4, (hipStream_t)stream, a);
-    return itermvs_launch_status();
+    return split3 ? launch_fused<corrnet_kernel<true>, kCnLdsFloats * 4>(grid, kCnThreads, (hipStream_t)stream, false, a)
+                  : launch_fused<corrnet_kernel<false>, kCnLdsFloats * 4>(grid, kCnThreads, (hipStream_t)stream, false, a);
 }
 
 extern "C" int itermvs_corrnet(const float* x, int64_t x_sn, const float* const* weights, const int32_t* seg_end, int32_t n_seg,

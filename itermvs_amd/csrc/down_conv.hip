@@ -22,6 +22,7 @@
 // Two such images: between two barriers a wave splits and stores tile i + 1 (fetched one iteration ago), multiplies tile i with
 // the loads of tile i + 2 spread over the taps (never a burst: DESIGN.md section 4, lat_conv), and stores tile i's results.
 #include "common.hpp"
+#include "tile_walk.hpp"
 
 namespace itermvs {
 
@@ -77,11 +78,11 @@ __global__ void __launch_bounds__(64 * NOB * PH) down_conv_kernel(const DownConv
     const uint32_t plane = (uint32_t)(a.H * a.W);
     const int P = a.Ho * a.Wo;
 
-    // this workgroup's run of tiles, in the order (image, tile column, tile row): a run walks down a column.  Workgroup b runs on
-    // XCD b % 8, so the runs of one XCD are neighbours in the tile list and share their halos in that XCD's L2
-    const int g = a.banded ? (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-    const int t0 = g * a.run + min(g, a.run_extra);
-    int left = a.run + (g < a.run_extra ? 1 : 0);             // tiles not yet fetched
+    // this workgroup's run of tiles, in the order (image, tile column, tile row): a run walks down a column.  Banded
+    // (tile_walk.hpp), the runs of one XCD are neighbours in the tile list and share their halos in that XCD's L2
+    const TileRun mine = tile_walk_run(a.run, a.run_extra, blockIdx.x, gridDim.x, a.banded);
+    const int t0 = mine.t0;
+    int left = mine.count;                                    // tiles not yet fetched
     auto advance = [&](DownTile t) {
         if (++t.ty == a.tiles_y) {
             t.ty = 0;
@@ -278,23 +279,13 @@ __global__ void __launch_bounds__(64 * NOB * PH) down_conv_kernel(const DownConv
 template <int CIN, int NOB, int PH, int TH>
 static int launch_down(DownConvArgs& a, int N, hipStream_t stream) {
     using G = DownGeom<CIN, NOB, PH, TH>;
-    auto kern = down_conv_kernel<CIN, NOB, PH, TH>;
-    static const bool attr_ok =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS) == hipSuccess;
-    ITERMVS_RETURN_IF(!attr_ok, ITERMVS_ERR_LAUNCH);
     a.tiles_x = (a.Wo + 15) / 16;
     a.tiles_y = (a.Ho + TH - 1) / TH;
-    const int64_t tiles = (int64_t)a.tiles_x * a.tiles_y * N;
-    ITERMVS_RETURN_IF(tiles > 0x7fffffff, ITERMVS_ERR_DIMS);
-    const int cus = itermvs_num_cus();                       // one workgroup per CU (the weights take 108 registers per lane)
-    int grid = (int)(tiles < cus ? tiles : cus);
-    if (grid >= 16) grid &= ~7;
-    a.run = (int)(tiles / grid); a.run_extra = (int)(tiles % grid);
-    a.banded = grid % 8 == 0;
-    itermvs_profile_begin(3, stream);          // bench.py's convolution roofline brackets this launch like an itermvs_conv2d one
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(G::THREADS), G::LDS, stream, a);
-    itermvs_profile_end(3, stream);
-    return itermvs_launch_status();
+    PersistentPlan plan;            // one workgroup per CU (the weights take 108 registers per lane)
+    const int rc = persistent_plan_cus((int64_t)a.tiles_x * a.tiles_y * N, 1, true, ITERMVS_WALK_RUNS, &plan);
+    if (rc != ITERMVS_OK) return rc;
+    a.run = plan.run; a.run_extra = plan.run_extra; a.banded = plan.banded;
+    return launch_fused<down_conv_kernel<CIN, NOB, PH, TH>, G::LDS>(dim3(plan.grid), G::THREADS, stream, true, a);
 }
 
 }  // namespace itermvs

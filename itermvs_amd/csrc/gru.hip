@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "tile_walk.hpp"
 
 namespace itermvs {
 
@@ -85,9 +86,9 @@ __global__ void __launch_bounds__(kGcThreads) gru_conv_kernel(const GruConvArgs 
     const int He = (a.H + 1) >> 1;
 
     // this workgroup's run of tiles
-    const int g = banded ? (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-    const int t0 = g * a.run + min(g, a.run_extra);           // (no 64-bit division in the prologue: the host splits the tile list)
-    int left = a.run + (g < a.run_extra ? 1 : 0);             // tiles not yet given to a pair
+    const TileRun mine = tile_walk_run(a.run, a.run_extra, blockIdx.x, gridDim.x, banded);
+    const int t0 = mine.t0;
+    int left = mine.count;                                    // tiles not yet given to a pair
     auto row_of = [&](int k) { return k < He ? 2 * k : 2 * (k - He) + 1; };
     auto second_ok = [&](int k) { return left > 1 && k + 1 != He && k + 1 != a.H; };
     auto advance = [&](GruPair t) {             // the pair after t; takes its tiles from ``left``
@@ -327,19 +328,10 @@ extern "C" int itermvs_gru_conv(const float* x, int64_t x_sb, int32_t B, int32_t
     a.out = out; a.out_sb = out_sb; a.out2 = out2; a.out2_sb = out2_sb;
     a.H = H; a.W = W; a.tiles_x = (W + 15) / 16;
     const int64_t tiles = (int64_t)a.tiles_x * H * B;
-    ITERMVS_RETURN_IF(tiles > 0x7fffffff, ITERMVS_ERR_DIMS);
-    static const bool attr_ok =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gru_conv_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, kGcLds) == hipSuccess &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gru_conv_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, kGcLds) == hipSuccess;
-    ITERMVS_RETURN_IF(!attr_ok, ITERMVS_ERR_LAUNCH);
-    const int cus = itermvs_num_cus();                       // one 8-wave workgroup per CU (256 registers per lane)
-    int grid = (int)(tiles < cus ? tiles : cus);
-    if (grid >= 16) grid &= ~7;
-    a.run = (int)(tiles / grid); a.run_extra = (int)(tiles % grid);
-    const int banded = grid % 8 == 0;     // workgroup b runs on XCD b % 8: neighbouring runs of tiles on one XCD
-    itermvs_profile_begin(3, (hipStream_t)stream);          // bench.py's convolution roofline brackets this launch like an itermvs_conv2d one
-    if (mode == 0) hipLaunchKernelGGL(gru_conv_kernel<4>, dim3(grid), dim3(kGcThreads), kGcLds, (hipStream_t)stream, a, (int)tiles, banded);
-    else hipLaunchKernelGGL(gru_conv_kernel<2>, dim3(grid), dim3(kGcThreads), kGcLds, (hipStream_t)stream, a, (int)tiles, banded);
-    itermvs_profile_end(3, (hipStream_t)stream);
-    return itermvs_launch_status();
+    PersistentPlan plan;            // one 8-wave workgroup per CU (256 registers per lane); banded: neighbouring runs of tiles on one XCD
+    const int rc = persistent_plan_cus(tiles, 1, true, ITERMVS_WALK_RUNS, &plan);
+    if (rc != ITERMVS_OK) return rc;
+    a.run = plan.run; a.run_extra = plan.run_extra;
+    return mode == 0 ? launch_fused<gru_conv_kernel<4>, kGcLds>(dim3(plan.grid), kGcThreads, (hipStream_t)stream, true, a, (int)tiles, plan.banded)
+                     : launch_fused<gru_conv_kernel<2>, kGcLds>(dim3(plan.grid), kGcThreads, (hipStream_t)stream, true, a, (int)tiles, plan.banded);
 }

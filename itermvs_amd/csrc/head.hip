@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "tile_walk.hpp"
 
 namespace itermvs {
 
@@ -665,25 +666,17 @@ extern "C" int itermvs_head_regress(const float* x, int64_t x_sb, int32_t B, int
                                     float* nd_out1, int64_t nd_sb1, int64_t* best, void* stream) {
     ITERMVS_RETURN_IF(!x || !w1_packed || !w2_packed || !bias2, ITERMVS_ERR_NULL);
     ITERMVS_RETURN_IF(B < 1 || P < 1, ITERMVS_ERR_DIMS);
-    static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(head_regress_kernel),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, kHeadLds) == hipSuccess;
-    ITERMVS_RETURN_IF(!attr_ok, ITERMVS_ERR_LAUNCH);
     HeadArgs a;
     a.x = x; a.x_sb = x_sb; a.w1p = w1_packed; a.w2p = w2_packed; a.bias2 = bias2;
     a.nd0 = nd_out0; a.nd1 = nd_out1; a.nd_sb0 = nd_sb0; a.nd_sb1 = nd_sb1; a.best = best; a.P = P;
-    hipLaunchKernelGGL(head_regress_kernel, dim3((P + 63) / 64, B), dim3(256), kHeadLds, (hipStream_t)stream, a);
-    return itermvs_launch_status();
+    return launch_fused<head_regress_kernel, kHeadLds>(dim3((P + 63) / 64, B), 256, (hipStream_t)stream, false, a);
 }
 
 template <bool CONF, bool W2B, bool C3 = false>
 static int launch_head_coop(const FusedArgs& a, int grid, int tiles, hipStream_t stream) {
     // CONF: 80 KB, C3: 71 KB -- two workgroups per CU still fit the 160 KB
     constexpr int lds = (kCoLds + (CONF ? kCoWc + 36 : 0) + (C3 ? 2 * (kC3T - kCoT) : 0)) * 4 + (C3 ? kC3WlB : 0);
-    auto kern = head_coop_kernel<CONF, W2B, C3>;
-    static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
-    if (!attr_ok) return ITERMVS_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, a, tiles);
-    return itermvs_launch_status();
+    return launch_fused<head_coop_kernel<CONF, W2B, C3>, lds>(dim3(grid), 256, stream, false, a, tiles);
 }
 
 static int launch_head_fused(const float* hidden, int64_t hidden_sb, int32_t B, int32_t H, int32_t W, const void* w0_tile, int32_t w0_format,
@@ -703,10 +696,12 @@ static int launch_head_fused(const float* hidden, int64_t hidden_sb, int32_t B, 
     a.H = H; a.W = W; a.tiles_x = (W + 15) / 16;
     a.wct = wc_tile; a.cdot = conf_dot; a.conf = conf; a.conf_sb = conf_sb;
     // one tile shared by the four waves of a persistent workgroup, two workgroups per CU
-    const int cus = itermvs_num_cus();
-    const int tiles = a.tiles_x * H * B;
     static const int wgs_per_cu = [] { const char* e = itermvs_tuning_env("ITERMVS_HEAD_WGS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 2; }();
-    const int grid = tiles < wgs_per_cu * cus ? tiles : wgs_per_cu * cus;
+    PersistentPlan plan;
+    const int64_t tiles64 = (int64_t)a.tiles_x * H * B;
+    const int rc = persistent_plan_cus(tiles64, wgs_per_cu, false, ITERMVS_WALK_PLAIN, &plan);
+    if (rc != ITERMVS_OK) return rc;
+    const int tiles = (int)tiles64, grid = plan.grid;
     hipStream_t st = (hipStream_t)stream;
     if (conf) return w2_format ? launch_head_coop<true, true>(a, grid, tiles, st) : launch_head_coop<true, false>(a, grid, tiles, st);
     if (w0_format == 3) return launch_head_coop<false, true, true>(a, grid, tiles, st);

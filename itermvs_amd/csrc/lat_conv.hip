@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "tile_walk.hpp"
 #include "conv_epilogue.hpp"
 
 namespace itermvs {
@@ -330,19 +331,10 @@ __global__ void __launch_bounds__(kLcThreads) lat_conv_kernel(const LatConvArgs 
     // tools/ubench/mfma_bf16_rate.hip); in lock step both would be in the same half at the same time.
     const bool b_first = wave < kLcWaves / 2;
 
-    // Tile order: workgroup b runs on XCD b % 8 (round-robin dispatch); the tiles of one XCD are a contiguous run of the tile list
-    // (whole image bands), so that tiles sharing halo rows / patch cache lines meet in the same 4 MB L2
-    int w, wstep, wend;
-    if (a.banded) {
-        const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-        w = (int)((int64_t)a.total * xcd / 8) + slot;
-        wend = (int)((int64_t)a.total * (xcd + 1) / 8);
-        wstep = gridDim.x >> 3;
-    } else {
-        w = blockIdx.x;
-        wend = a.total;
-        wstep = gridDim.x;
-    }
+    // Tile order (tile_walk.hpp): banded, tiles that share halo rows / coarse-patch cache lines meet in one XCD's L2
+    const TileWalk walk = tile_walk_strided(a.total, blockIdx.x, gridDim.x, 0, a.banded);
+    int w = walk.w;
+    const int wstep = walk.wstep, wend = walk.wend;
     if (w >= wend) return;
     Work cur = decode(w);
 #pragma unroll
@@ -433,20 +425,15 @@ __global__ void __launch_bounds__(kLcThreads) lat_conv_kernel(const LatConvArgs 
 }
 
 template <int KS, int MBO>
-static int launch_lat_conv(LatConvArgs& a, hipStream_t stream) {
+static int launch_lat_conv(LatConvArgs& a, int64_t total, hipStream_t stream) {
     constexpr int lds = 2 * kLcChunkB + MBO * 3 * kLcWChunk + kLcPPX * kLcPS * 4 + 4 * KS * kLcMH * kLcFW * 4;
     static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = lat_conv_kernel<KS, MBO>;
-    static const bool attr_ok =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
-    if (!attr_ok) return ITERMVS_ERR_LAUNCH;
-    const int cus = itermvs_num_cus();
-    const int grid = a.total < cus ? a.total : cus;
-    a.banded = grid % 8 == 0 && a.total >= grid ? 1 : 0;          // (grid < 8 or ragged: plain order)
-    itermvs_profile_begin(3, stream);           // bench.py's convolution roofline brackets this launch like an itermvs_conv2d one
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kLcThreads), lds, stream, a);
-    itermvs_profile_end(3, stream);
-    return itermvs_launch_status();
+    PersistentPlan plan;
+    const int rc = persistent_plan_cus(total, 1, false, ITERMVS_WALK_STRIDED, &plan);
+    if (rc != ITERMVS_OK) return rc;
+    a.total = (int)total;
+    a.banded = plan.banded;
+    return launch_fused<lat_conv_kernel<KS, MBO>, lds>(dim3(plan.grid), kLcThreads, stream, true, a);
 }
 
 }  // namespace itermvs
@@ -471,8 +458,5 @@ extern "C" int itermvs_lateral_conv3x3(const float* fine, int64_t fine_sn, int32
     a.fine_sn = fine_sn; a.coarse_sn = coarse_sn; a.out_sn = out_sn;
     a.N = N; a.H = H; a.W = W; a.Cout = Cout; a.CoutPad = (Cout + 15) / 16 * 16; a.out_nhwc = out_layout;
     a.tiles_x = (W + kLcTW - 1) / kLcTW; a.tiles_y = (H + kLcTH - 1) / kLcTH;
-    const int64_t total = (int64_t)N * a.tiles_x * a.tiles_y;
-    ITERMVS_RETURN_IF(total >= ((int64_t)1 << 31), ITERMVS_ERR_DIMS);
-    a.total = (int)total;
-    return launch_lat_conv<4, 1>(a, (hipStream_t)stream);
+    return launch_lat_conv<4, 1>(a, (int64_t)N * a.tiles_x * a.tiles_y, (hipStream_t)stream);
 }

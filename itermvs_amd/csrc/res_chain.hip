@@ -16,6 +16,7 @@
 // positions (row-major over the layer's region) and reads three A operands per tap and two 16-byte B operands per tap and group.  Activations are split ONCE, when they are produced: LDS tiles [plane h, m, l][half][position][8 bf16] like
 // conv_tile3's.  The skip of the third layer is a = h + m + l rebuilt exactly from its LDS tile.
 #include "common.hpp"
+#include "tile_walk.hpp"
 
 namespace itermvs {
 
@@ -195,20 +196,11 @@ __global__ void __launch_bounds__(kRcThreads) res_chain16_kernel(const ResChainA
     };
 
     static_assert(NIT == 3, "one staging item per layer");
-    // Tile order: workgroup b runs on XCD b % 8 (round-robin dispatch); the tiles of one XCD are a contiguous run of the tile list
-    // (whole image bands): tiles that share halo rows (a tile's inputs are 2.1x / 1.7x its outputs) meet in the same 4 MB L2
-    // instead of being fetched from the fabric once per XCD (HBM traffic 149 MB per launch in plain order for 78 MB of tensors)
-    int w, wstep, wend;
-    if (a.banded) {
-        const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-        w = (int)((int64_t)a.total * xcd / 8) + slot;
-        wend = (int)((int64_t)a.total * (xcd + 1) / 8);
-        wstep = gridDim.x >> 3;
-    } else {
-        w = blockIdx.x;
-        wend = a.total;
-        wstep = gridDim.x;
-    }
+    // Tile order (tile_walk.hpp).  Banding pays here because a tile's inputs are 2.1x / 1.7x its outputs: in plain order the halo
+    // rows are fetched from the fabric once per XCD (HBM traffic 149 MB per launch for 78 MB of tensors)
+    const TileWalk walk = tile_walk_strided(a.total, blockIdx.x, gridDim.x, 0, a.banded);
+    int w = walk.w;
+    const int wstep = walk.wstep, wend = walk.wend;
     if (w >= wend) return;
     Work cur = decode(w);
 #pragma unroll
@@ -370,18 +362,11 @@ extern "C" int itermvs_res_chain16(const float* y1, int64_t y1_sn, const float* 
     a.N = N; a.H = H; a.W = W;
     a.tiles_x = (W + TW - 1) / TW; a.tiles_y = (H + TH - 1) / TH;
     const int64_t total = (int64_t)N * a.tiles_x * a.tiles_y;
-    ITERMVS_RETURN_IF(total >= ((int64_t)1 << 31), ITERMVS_ERR_DIMS);
+    PersistentPlan plan;
+    const int rc = persistent_plan_cus(total, 1, false, ITERMVS_WALK_STRIDED, &plan);
+    if (rc != ITERMVS_OK) return rc;
     a.total = (int)total;
-    static const bool attr_ok =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(res_chain16_kernel<TH, TW, false>), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS) == hipSuccess &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(res_chain16_kernel<TH, TW, true>), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS) == hipSuccess;
-    ITERMVS_RETURN_IF(!attr_ok, ITERMVS_ERR_LAUNCH);
-    const int cus = itermvs_num_cus();
-    const int grid = a.total < cus ? a.total : cus;
-    a.banded = grid % 8 == 0 && a.total >= grid ? 1 : 0;          // (grid < 8 or ragged: plain order)
-    itermvs_profile_begin(3, (hipStream_t)stream);          // bench.py's convolution roofline brackets this launch like an itermvs_conv2d one
-    if (in_layout) hipLaunchKernelGGL((res_chain16_kernel<TH, TW, true>), dim3(grid), dim3(kRcThreads), G::LDS, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((res_chain16_kernel<TH, TW, false>), dim3(grid), dim3(kRcThreads), G::LDS, (hipStream_t)stream, a);
-    itermvs_profile_end(3, (hipStream_t)stream);
-    return itermvs_launch_status();
+    a.banded = plan.banded;
+    return in_layout ? launch_fused<res_chain16_kernel<TH, TW, true>, G::LDS>(dim3(plan.grid), kRcThreads, (hipStream_t)stream, true, a)
+                     : launch_fused<res_chain16_kernel<TH, TW, false>, G::LDS>(dim3(plan.grid), kRcThreads, (hipStream_t)stream, true, a);
 }

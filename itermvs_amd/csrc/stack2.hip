@@ -17,6 +17,7 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "tile_walk.hpp"
 
 namespace itermvs {
 
@@ -331,10 +332,9 @@ extern "C" int itermvs_conv3x3_conv1x1(const float* x, int64_t x_sb, int32_t B, 
     a.x = x; a.x_sb = x_sb; a.w0t = w0_tile; a.w1p = w1_packed; a.bias = bias1; a.out = out; a.out_sb = out_sb;
     a.H = H; a.W = W; a.tiles_x = (W + 15) / 16; a.NO = NO; a.NOB = (NO + 15) / 16;
     const int64_t tiles = (int64_t)a.tiles_x * H * B;
-    ITERMVS_RETURN_IF(tiles > 0x7fffffff, ITERMVS_ERR_DIMS);
-    const int resident = 2 * itermvs_num_cus();          // one tile shared by the four waves of a persistent workgroup, two per CU
-    const int grid = (int)(tiles < resident ? tiles : resident);
-    if (weight_format == 3) hipLaunchKernelGGL(stack2_coop_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, (int)tiles);
-    else hipLaunchKernelGGL(stack2_coop_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, (int)tiles);
-    return itermvs_launch_status();
+    PersistentPlan plan;            // one tile shared by the four waves of a persistent workgroup, two per CU
+    const int rc = persistent_plan_cus(tiles, 2, false, ITERMVS_WALK_PLAIN, &plan);
+    if (rc != ITERMVS_OK) return rc;
+    return weight_format == 3 ? launch_fused<stack2_coop_kernel<true>, 0>(dim3(plan.grid), 256, (hipStream_t)stream, false, a, (int)tiles)
+                              : launch_fused<stack2_coop_kernel<false>, 0>(dim3(plan.grid), 256, (hipStream_t)stream, false, a, (int)tiles);
 }

@@ -18,6 +18,7 @@
 // vector instructions do not overlap on this chip: 43-45 us against 72 us for the two launches.
 #include "common.hpp"
 #include "compose.hpp"
+#include "tile_walk.hpp"
 #include <cstdlib>
 
 namespace itermvs {
@@ -99,17 +100,10 @@ __global__ __launch_bounds__(kStThreads) void stem_kernel(StemArgs a, int tiles,
         compose_proj_body(comp, (int)blockIdx.x * kStThreads + (int)threadIdx.x);
         return;
     }
-    // Tile order: workgroup b runs on XCD b % 8 (round-robin dispatch); the tiles of one XCD are a contiguous run of the tile list
-    // (whole image bands), so that the image rows two vertically adjacent tiles share meet in the same 4 MB L2.  (The n_comp
-    // composing workgroups in front shift which workgroups an XCD gets, not the rule.)
-    int tile0 = (int)blockIdx.x - n_comp, tstep = (int)gridDim.x - n_comp, tend = tiles;
-    if (tstep >= 8) {
-        const int b = (int)blockIdx.x, xcd = b & 7;
-        const int first = n_comp + ((xcd - n_comp) & 7);             // the XCD's first tile workgroup
-        tile0 = (int)((int64_t)tiles * xcd / 8) + ((b - first) >> 3);
-        tend = (int)((int64_t)tiles * (xcd + 1) / 8);
-        tstep = ((int)gridDim.x - 1 - first) / 8 + 1;
-    }
+    // Tile order (tile_walk.hpp), banded from 8 tile workgroups on: the image rows two vertically adjacent tiles share meet in one
+    // XCD's L2.  (The n_comp composing workgroups in front shift which workgroups an XCD gets, not the rule.)
+    const TileWalk walk = tile_walk_strided(tiles, blockIdx.x, gridDim.x, n_comp, (int)gridDim.x - n_comp >= 8);
+    const int tile0 = walk.w, tstep = walk.wstep, tend = walk.wend;
 
     constexpr int kStIR = 2 * kStTH + 3, kStFR = 2 * kStTH + 1;      // image / f0 patch rows
     constexpr int kStFPL = kStFR * kStFP + 1;                        // odd plane stride (1123 / 595)
@@ -258,11 +252,14 @@ static int launch_stem(const float* x, int64_t x_sn, int32_t M, int32_t H, int32
     static const int th = [] { const char* e = itermvs_tuning_env("ITERMVS_STEM_TH"); return e && atoi(e) == 4 ? 4 : 8; }();
     a.tiles_x = (a.W2 + kStTW - 1) / kStTW; a.tiles_y = (a.H2 + th - 1) / th;
     const int64_t tiles = (int64_t)M * a.tiles_x * a.tiles_y;
-    if (tiles > 0x7fffffff) return ITERMVS_ERR_DIMS;
-    // persistent workgroups, tiles round-robin: as many as stay resident (LDS 51 / 28 KB per workgroup)
+    // persistent workgroups: as many as stay resident (LDS 51 / 28 KB per workgroup), behind the n_comp composing ones
     static const int wg_per_cu = [] { const char* e = itermvs_tuning_env("ITERMVS_STEM_WGS"); return e ? atoi(e) : 0; }();
-    const int resident = itermvs_num_cus() * (wg_per_cu > 0 ? wg_per_cu : (th == 4 ? 4 : 3));
-    const unsigned grid = (unsigned)(tiles < resident ? tiles : resident) + (unsigned)n_comp;
+    PersistentPlan plan = {};       // (M == 0: the composing workgroups alone)
+    if (tiles != 0) {
+        const int rc = persistent_plan_cus(tiles, wg_per_cu > 0 ? wg_per_cu : (th == 4 ? 4 : 3), false, ITERMVS_WALK_STRIDED_LEAD, &plan);
+        if (rc != ITERMVS_OK) return rc;
+    }
+    const unsigned grid = (unsigned)plan.grid + (unsigned)n_comp;
     if (th == 4) hipLaunchKernelGGL(stem_kernel<4>, dim3(grid), dim3(kStThreads), 0, (hipStream_t)stream, a, (int)tiles, n_comp, c);
     else hipLaunchKernelGGL(stem_kernel<8>, dim3(grid), dim3(kStThreads), 0, (hipStream_t)stream, a, (int)tiles, n_comp, c);
     return itermvs_launch_status();

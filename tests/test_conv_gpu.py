@@ -4,6 +4,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import walk_shapes
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
@@ -108,10 +110,18 @@ def test_conv_without_residual_or_bias(case, act):
     assert torch.equal(dense, got)
 
 
-@pytest.mark.parametrize("case", CASES)
+@pytest.mark.parametrize("case", CASES + list(walk_shapes.CONV_REGIMES))
 @pytest.mark.parametrize("act", ["none", "relu"])
 @pytest.mark.parametrize("fmt", ["mfma", "valu"])
-def test_conv_matches_torch(case, act, fmt):
+def test_conv_matches_torch(case, act, fmt, conv_arithmetic):
+    plan = None
+    if isinstance(case, str):
+        # a regime of the persistent tile walk on one 16 -> 16 layer: conv_tile3 runs it in 8 x 32 tiles, conv_tile in 4 x 32, one
+        # channel block (the plan, checked below, says so)
+        from itermvs_amd import _lib
+        plan, th = _lib.ConvPlan(), 8 if conv_arithmetic == "bf16x3" else 4
+        n, h, w = walk_shapes.walk_shape(case, th, 32)
+        case = (16, 16, 3, 1, 1, 1, h, w, n)
     cin, cout, k, stride, pad, dil, h, w, n = case
     gen = torch.Generator().manual_seed(cin * 100 + cout)
     x = torch.randn((n, cin, h, w), generator=gen).to(DEV)
@@ -122,9 +132,11 @@ def test_conv_matches_torch(case, act, fmt):
     want = want + add
     if act == "relu":
         want = F.relu(want)
-    got = ops().conv2d(x, packed(wt, fmt), b, ksize=k, stride=stride, pad=pad, dilation=dil, act=act, add=add)
+    got = ops().conv2d(x, packed(wt, fmt), b, ksize=k, stride=stride, pad=pad, dilation=dil, act=act, add=add, plan=plan)
     assert got.shape == want.shape
     assert rel_err(got, want) <= 2e-6
+    if plan is not None and fmt == "mfma":
+        assert (plan.TH, 16 * plan.TWT, plan.ncb) == (th, 32, 1) and plan.total == n * -(-h // th) * -(-w // 32), str(plan)
 
 
 # name, back end per conv_arithmetic (bf16x3, fp32), cin, cout, what
@@ -353,13 +365,16 @@ def test_relu_dot_epilogue_is_conv_relu_conv1x1():
     assert got.shape == want.shape == (2, 1, 37, 50) and float((got - want).abs().max()) <= 2e-6
 
 
-@pytest.mark.parametrize("case", [(5, 512, 640), (2, 96, 160), (1, 50, 70), (3, 16, 64), (1, 7, 5)])
+@pytest.mark.parametrize("case", [(5, 512, 640), (2, 96, 160), (1, 50, 70), (3, 16, 64), (1, 7, 5)] + list(walk_shapes.REGIMES))
 def test_stem_one_launch_matches_torch(case):
     """itermvs_stem (FeatureNet.conv1 + layer1[0].conv1 / .downsample, net.py:13-14,39-40, fea0 kept in LDS) against the
     torch layer chain with BatchNorm folded: full cfg-1 size, ragged sizes (odd, not multiples of the 8 x 32 tile) and an
     image smaller than a tile; zero padding of fea0 at the image border must be reproduced"""
     from conftest import load_weights
     from itermvs_amd.engine import fold_batchnorm
+    if isinstance(case, str):       # a regime of the tile walk: 8 x 32 tiles at half resolution, three workgroups per CU resident
+        m, h2, w2 = walk_shapes.walk_shape(case, 8, 32, per_cu=3)
+        case = (m, 2 * h2 - 1, 2 * w2 - 1)
     m, h, w = case
     wts = {k: v.to(DEV) for k, v in load_weights("dtu").items() if k.startswith("feature_net.")}
     (w0, b0), (w1, b1), (wd, bd) = [fold_batchnorm(wts, "feature_net." + n) for n in ("conv1.", "layer1.0.conv1.", "layer1.0.downsample.")]
@@ -379,13 +394,13 @@ def test_stem_one_launch_matches_torch(case):
         ops().stem(torch.zeros((1, 4, 8, 8), device=DEV), *ops().pack_stem_weights(w0, b0, w1, b1, wd, bd))
 
 
-@pytest.mark.parametrize("case", [(5, 256, 320), (2, 37, 70), (1, 8, 32), (3, 64, 96), (1, 5, 3)])
+@pytest.mark.parametrize("case", [(5, 256, 320), (2, 37, 70), (1, 8, 32), (3, 64, 96), (1, 5, 3)] + list(walk_shapes.REGIMES))
 def test_res_chain16_one_launch_matches_torch(case, conv_arithmetic):
     """itermvs_res_chain16: FeatureNet.layer1 behind the stem (module.py:33-50, net.py:13,40) in one launch against the three
     torch layers in fp64, and against the three-launch form of this library (same bf16x3 arithmetic per layer)"""
     if conv_arithmetic != "bf16x3":
         pytest.skip("the chain exists in the bf16x3 arithmetic only (the fp32 form keeps its three launches)")
-    n, h, w = case
+    n, h, w = walk_shapes.walk_shape(case, 8, 32) if isinstance(case, str) else case         # (a regime of the tile walk: 8 x 32 tiles)
     g = torch.Generator().manual_seed(n * 1000 + h)
     y1 = torch.randn((n, 16, h, w), generator=g).relu().to(DEV)
     sc = torch.randn((n, 16, h, w), generator=g).to(DEV)
@@ -419,15 +434,15 @@ def test_res_chain16_one_launch_matches_torch(case, conv_arithmetic):
         ops().res_chain16(y1, sc, [ops().MfmaWeight(wt, split3=False) for wt in wts], bs)
 
 
-@pytest.mark.parametrize("case", [(5, 256, 320), (2, 38, 70), (1, 8, 32), (3, 64, 96), (1, 2, 2), (1, 10, 34)])
+@pytest.mark.parametrize("case", [(5, 256, 320), (2, 38, 70), (1, 8, 32), (3, 64, 96), (1, 2, 2), (1, 10, 34)] + list(walk_shapes.REGIMES))
 @pytest.mark.parametrize("storage", ["planes", "fp32", "fp16", "bf16"])
 def test_lateral_conv3x3_one_launch_matches_torch(case, storage):
     """itermvs_lateral_conv3x3 (net.py:48-50: F.interpolate x2 + inner1, then output1, the 48-channel map kept on the chip) against
     the torch layers in fp64 and against the two-launch form of this library (fused-interpolate lateral layer, then the bf16x3
     3x3 layer): full level-1 size of cfg 1, ragged sizes, images smaller than a tile; every output storage form"""
-    n, h, w = case
     if storage != "planes" and case not in ((5, 256, 320), (2, 38, 70), (1, 2, 2)):
         pytest.skip("storage forms: three shapes")
+    n, h, w = walk_shapes.walk_shape(case, 8, 32, ragged=2) if isinstance(case, str) else case  # (a regime of the tile walk; even sizes)
     g = torch.Generator().manual_seed(n * 977 + h + w)
     fine = torch.randn((n, 16, h, w), generator=g).relu().to(DEV)
     coarse = torch.randn((n, 48, h // 2, w // 2), generator=g).to(DEV)

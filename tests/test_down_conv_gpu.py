@@ -4,6 +4,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import walk_shapes
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 PAIRS = [(16, 32), (32, 48)]        # (Cin, C): layer2.0 and layer3.0
@@ -63,6 +65,7 @@ SHAPES = [(1, 2, 2),        # smaller than any tile, every tap but the centre pa
           (2, 38, 70),      # ragged in both directions, several tiles, two images
           (3, 64, 96),      # whole tiles, more than one tile per column
           "persistent"]     # more tiles than workgroups: a workgroup walks several tiles and crosses an image boundary
+SHAPES += list(walk_shapes.REGIMES)     # the regimes of the tile walk (TILE_ROWS x 16 output pixels per tile)
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=str)
@@ -70,6 +73,9 @@ SHAPES = [(1, 2, 2),        # smaller than any tile, every tap but the centre pa
 def test_down_conv_matches_fp64_and_the_conv2d_launch(pair, shape):
     """both results within 3e-6 of torch's fp64 convolution and within 2e-6 of this library's fp32-MFMA launch"""
     cin, c = pair
+    if shape in walk_shapes.REGIMES:
+        n, ho, wo = walk_shapes.walk_shape(shape, TILE_ROWS[cin], TILE_COLS)
+        shape = (n, 2 * ho, 2 * wo - 1)
     n, h, w = persistent_shape(cin) if shape == "persistent" else shape
     x, wt, b = make(cin, c, n, h, w)
     want_y, want_s = reference(x, wt, b, c)

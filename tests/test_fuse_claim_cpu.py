@@ -124,7 +124,7 @@ def test_claim_entry_point_is_declared_bound_and_documented():
     from itermvs_amd import _lib
     header = open(os.path.join(ROOT, "include", "itermvs_hip.h")).read()
     lib = _lib.load()
-    assert hasattr(lib, "itermvs_fuse_depth_claim") and lib.itermvs_version() == _lib.ABI_VERSION == 19
+    assert hasattr(lib, "itermvs_fuse_depth_claim") and lib.itermvs_version() == _lib.ABI_VERSION == 20
     plain, claim = _lib.PROTOTYPES["itermvs_fuse_depth"], _lib.PROTOTYPES["itermvs_fuse_depth_claim"]
     assert claim[1][:16] == plain[1][:16] and len(claim[1]) == len(plain[1]) + 2      # the same arguments plus the two map arguments
     doc = header.split("itermvs_fuse_depth_claim --")[1].split("*/")[0]

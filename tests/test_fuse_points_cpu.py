@@ -21,7 +21,7 @@ def test_fuse_points_is_declared_bound_and_exported():
     for name in ("itermvs_fuse_points", "itermvs_fuse_points_workspace_bytes"):
         assert name in declared and name in _lib.PROTOTYPES and hasattr(lib, name)
     assert "eval.py:287-308" in header
-    assert lib.itermvs_version() == _lib.ABI_VERSION == 19
+    assert lib.itermvs_version() == _lib.ABI_VERSION == 20
     assert len(_lib.PROTOTYPES["itermvs_fuse_points"][1]) == 15
     makefile = open(os.path.join(ROOT, "itermvs_amd", "csrc", "Makefile")).read()
     assert makefile.count("fuse_points.hip") == 2                       # SRCS and the resource-usage list

@@ -5,6 +5,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import walk_shapes
 from conftest import golden, load_weights
 from oracle import itermvs_oracle as O
 
@@ -1015,14 +1016,14 @@ def test_conv3x3_conv1x1_one_launch_matches_torch(head, size):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("size", [(1, 128, 160), (2, 37, 53), (1, 3, 9), (3, 64, 80)])
+@pytest.mark.parametrize("size", [(1, 128, 160), (2, 37, 53), (1, 3, 9), (3, 64, 80)] + list(walk_shapes.REGIMES))
 def test_gru_conv_matches_the_torch_gru(size):
     """itermvs_gru_conv (csrc/gru.hip) against the reference's ConvGRU (models/module.py:53-66: dilated 3x3 gates over
     [h | normalised depth | scores], 43 channels) in float64: z, r*h and the updated state, bf16x3 arithmetic -- 2e-6 of the
     pre-activation range on every output; and against the two itermvs_conv2d launches it replaces.  Ragged widths, maps smaller than
     a tile, more tiles than workgroups, outputs written into channel slices of wider buffers, the state updated in place"""
     import torch.nn.functional as F
-    b, h, w = size
+    b, h, w = walk_shapes.walk_shape(size, 1, 16) if isinstance(size, str) else size          # (a regime of the tile walk: 1 x 16 tiles)
     wts = load_weights("dtu")
     p = "iter_mvs.update.gru."
     wz, wr, wq = (cu(wts[p + f"conv{k}.weight"]) for k in "zrq")

@@ -242,7 +242,7 @@ def test_new_entry_points_are_declared_bound_and_exported():
         assert re.search(r"^int %s\(" % name, header, re.M), name
         assert name in _lib.PROTOTYPES, name
         assert hasattr(lib, name), name
-    assert "#define ITERMVS_ABI_VERSION 19" in header and lib.itermvs_version() == 19
+    assert "#define ITERMVS_ABI_VERSION 20" in header and lib.itermvs_version() == 20
     mk = open(os.path.join(ROOT, "itermvs_amd", "csrc", "Makefile")).read()
     assert mk.count("cloud_register.hip") == 2
 
