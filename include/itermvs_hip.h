@@ -94,6 +94,7 @@ typedef struct itermvs_level_src {
  * NaN -- the deferred form of the reference's host-side asserts (module.py:83,87).
  * When `inv_min` != NULL the same launch also writes the inverse depth range of the batch,
  * inv_min[b] = 1 / depth_min[b], inv_max[b] = 1 / depth_max[b] (models/itermvs.py:240-241), b < B.
+ * ITERMVS_ERR_DIMS: n_sets * (V - 1) > 2^31 - 1.
  * ------------------------------------------------------------------------------------------ */
 int itermvs_compose_proj(const float* mats, int32_t n_sets, int32_t V, float* out,
                          int32_t* nan_flag, const float* depth_min, const float* depth_max,
@@ -106,13 +107,17 @@ int itermvs_compose_proj(const float* mats, int32_t n_sets, int32_t V, float* ou
  * `mask` != NULL, the validity mask [B,N,H,W] as uint8.  `proj` = [B,12] from
  * itermvs_compose_proj.  Any strides / any C.  Kept for API completeness and unit tests;
  * the engine itself never materialises the warped volume.
+ * Limits of the one-thread-per-item launches (here and below; ITERMVS_ERR_DIMS before any launch): the item count of a
+ * 256-thread launch is at most 2^32 - 256 (gridDim.x * blockDim.x < 2^32), a batch or view count carried in grid.y at most
+ * 65535, and 2^31 - 1 items where the kernel indexes in 32 bits.  Here: B * N * H * W <= 2^32 - 256.
  * ------------------------------------------------------------------------------------------ */
 int itermvs_warp(const itermvs_fmap* src, const float* proj, const float* depth,
                  int32_t B, int32_t N, int32_t H, int32_t W, float* out, uint8_t* mask,
                  void* stream);
 
 /* gradient of itermvs_warp w.r.t. src (grid math is no_grad in the reference, module.py:77):
- * grad_src[B,C,H1,W1] (contiguous NCHW, must be zero-filled) += scatter of grad_out[B,C,N,H,W] */
+ * grad_src[B,C,H1,W1] (contiguous NCHW, must be zero-filled) += scatter of grad_out[B,C,N,H,W]
+ * B * N * H * W <= 2^32 - 256, H1 * W1 <= 2^31 - 1. */
 int itermvs_warp_backward(const float* grad_out, const float* proj, const float* depth,
                           int32_t B, int32_t C, int32_t N, int32_t H, int32_t W,
                           int32_t H1, int32_t W1, float* grad_src, void* stream);
@@ -285,24 +290,25 @@ int itermvs_corr_init_backward(const itermvs_corr_init_params* p, const float* g
 
 /* itermvs_view_aggregate -- models/itermvs.py:59-69
  *   out[b,n,g,p] = sum_s corr[b,s,n,g,p] * w[b,s,p] / (1e-5 + sum_s w[b,s,p])
- * corr [B,S,N,8,P], w [B,S,P] (PixelViewWeight output at 1/8 res), out [B,N,8,P]. */
+ * corr [B,S,N,8,P], w [B,S,P] (PixelViewWeight output at 1/8 res), out [B,N,8,P].  8 * B * N * P <= 2^31 - 1. */
 int itermvs_view_aggregate(const float* corr, const float* w, int32_t S, int32_t B, int32_t N,
                            int32_t P, float* out, void* stream);
 /* itermvs_view_aggregate_up -- the same, and in the SAME launch (extra blocks: two independent pieces of work that only
  * read w) the x2 bilinear up-sampling of the view weights the iterations use (models/itermvs.py:56-57,71):
  *   w [B,S,H3,W3] -> w_up [B,S,2*H3,2*W3], or, with w_up_interleaved != 0, the same values stored [B,2*H3,2*W3,S] (the
  *   layout itermvs_corr_iter reads fastest: view_w_ss = 1, view_w_sp = S).
- *   corr_layout: 0 = corr [B,S,N,8,P]; 1 = groups last [B,S,N,P,8] (itermvs_corr_init's out_layout 1; 16-byte aligned). */
+ *   corr_layout: 0 = corr [B,S,N,8,P]; 1 = groups last [B,S,N,P,8] (itermvs_corr_init's out_layout 1; 16-byte aligned).
+ *   8 * B * N * H3 * W3 <= 2^31 - 1, 4 * B * S * H3 * W3 <= 2^32 - 256, and the two pieces together at most 2^24 - 1 blocks of 256. */
 int itermvs_view_aggregate_up(const float* corr, int32_t corr_layout, const float* w, int32_t S, int32_t B, int32_t N, int32_t H3,
                               int32_t W3, float* out, float* w_up, int32_t w_up_interleaved, void* stream);
 
 /* itermvs_softmax_max -- models/itermvs.py:347-348 (PixelViewWeight tail)
- *   out[m,p] = max_n softmax_n(x[m,n,p]);  x [M,N,P] contiguous, out [M,P]. */
+ *   out[m,p] = max_n softmax_n(x[m,n,p]);  x [M,N,P] contiguous, out [M,P].  M * P <= 2^32 - 64 (N <= 32), 2^32 - 256 (N > 32). */
 int itermvs_softmax_max(const float* x, int32_t M, int32_t N, int32_t P, float* out, void* stream);
 
 /* itermvs_pvw_tail -- models/itermvs.py:343-348 (PixelViewWeight after its 3x3 layer), fused:
  *   out[m,p] = max_n softmax_n( sum_c w[c] * x[m*N+n, c, p] + bias )
- * x [M*N, C, P] planes (C = 16, N <= 32), w [C], bias [1] or NULL, out [M,P]. */
+ * x [M*N, C, P] planes (C = 16, N <= 32), w [C], bias [1] or NULL, out [M,P].  P <= 2^29 - 64, M <= 65535 (grid.y). */
 int itermvs_pvw_tail(const float* x, const float* w, const float* bias, int32_t M, int32_t N, int32_t C,
                      int32_t P, float* out, void* stream);
 
@@ -315,6 +321,7 @@ int itermvs_pvw_tail(const float* x, const float* w, const float* bias, int32_t 
  *   nd_out0 / nd_out1: two destinations for the normalised depth, written at
  *     nd_outX[b*nd_sbX + p] (lets the GRU input buffers be filled in place);
  *   prob [B,256,P] contiguous (training / API parity);  best [B,P] int64 arg-max index.
+ * P <= 2^29 - 32, B <= 65535 (grid.y).
  * ------------------------------------------------------------------------------------------ */
 int itermvs_prob_regress(const float* logits, int64_t sb, int64_t sc, int64_t sp, int32_t B,
                          int32_t P, float* nd_out0, int64_t nd_sb0, float* nd_out1,
@@ -454,6 +461,7 @@ int itermvs_gru_conv(const float* x, int64_t x_sb, int32_t B, int32_t H, int32_t
  * h / rh are addressed as base + b*sb + c*P + p so they can live inside the [B,43,P]
  * concatenated GRU input buffers.  itermvs_gru_out updates h in place and, when h_copy != NULL,
  * also stores the new state contiguously at h_copy[B,hid,P] (input of the depth / confidence head convolutions).
+ * B * hid * P <= 2^32 - 256.
  * ------------------------------------------------------------------------------------------ */
 int itermvs_gru_rh(const float* zr, const float* h, int64_t h_sb, float* rh, int64_t rh_sb,
                    int32_t B, int32_t hid, int32_t P, void* stream);
@@ -461,7 +469,7 @@ int itermvs_gru_out(const float* zr, const float* q, float* h, int64_t h_sb, flo
                     int32_t B, int32_t hid, int32_t P, void* stream);
 
 /* itermvs_pack_scores -- models/itermvs.py:122-124,193: concatenates the three CorrNet outputs
- * ([B,N_l,P] each) into channels [ch0, ch0+N0+N1+N2) of up to two [B,Ctot,P] buffers. */
+ * ([B,N_l,P] each) into channels [ch0, ch0+N0+N1+N2) of up to two [B,Ctot,P] buffers.  B * (N0+N1+N2) * P <= 2^31 - 1. */
 int itermvs_pack_scores(const float* s0, const float* s1, const float* s2, const int32_t N[3],
                         int32_t B, int32_t P, float* dst0, float* dst1, int64_t dst_sb,
                         int32_t ch0, void* stream);
@@ -473,20 +481,22 @@ int itermvs_pack_scores(const float* s0, const float* s1, const float* s2, const
  *   nd     [B,1,H,W] at nd + b*nd_sb + y*W + x
  *   depth  [B,1,4H,4W] contiguous = 1/(inv_max + up*(inv_min-inv_max));
  *   when `norm_out` != NULL the un-normalised convex combination is also stored there.
+ *   4 * B * H * W <= 2^31 - 1.
  * ------------------------------------------------------------------------------------------ */
 int itermvs_convex_upsample(const float* logits, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
                             const float* nd, int64_t nd_sb, const float* inv_depth_min,
                             const float* inv_depth_max, int32_t B, int32_t H, int32_t W,
                             float* depth, float* norm_out, void* stream);
 /* itermvs_final_upsample -- itermvs_convex_upsample (depth, models/itermvs.py:321-322) and, in the SAME launch, the x4 bilinear
- * up-sampling of the confidence (models/itermvs.py:323-324): conf [M,H,W] -> conf_up [M,4H,4W]. */
+ * up-sampling of the confidence (models/itermvs.py:323-324): conf [M,H,W] -> conf_up [M,4H,4W].
+ * 4 * B * H * W <= 2^31 - 1, 16 * M * H * W <= 2^32 - 256, and the two pieces together at most 2^24 - 1 blocks of 256. */
 int itermvs_final_upsample(const float* logits, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float* nd, int64_t nd_sb,
                            const float* inv_depth_min, const float* inv_depth_max, int32_t B, int32_t H, int32_t W, float* depth,
                            const float* conf, int32_t M, float* conf_up, void* stream);
 
 /* itermvs_bilinear_up -- F.interpolate(x, scale_factor=s, mode='bilinear') for integer s
  * (models/itermvs.py:56,161,323): x [M,H,W] -> out [M,s*H,s*W]; `act`: 0 none, 1 tanh
- * (hidden_init, itermvs.py:162). */
+ * (hidden_init, itermvs.py:162).  M * H * W * s^2 <= 2^32 - 256 (itermvs_bilinear_up2: B * C * H * W * s^2). */
 int itermvs_bilinear_up(const float* x, int32_t M, int32_t H, int32_t W, int32_t scale,
                         int32_t act, float* out, void* stream);
 /* same for x [B,C,H,W] with up to two destinations given as [C,sH,sW] planes at batch strides out_sb / out2_sb

@@ -144,9 +144,7 @@ extern "C" int itermvs_cloud_cell_keys(const float* xyz, int64_t n, double ox, d
     const int bad = check_grid(n, ox, oy, oz, nx, ny, nz, edge);
     ITERMVS_RETURN_IF(bad, bad);
     const CloudGrid g{ox, oy, oz, edge, nx, ny, nz};
-    hipLaunchKernelGGL(cloud_cell_keys_kernel, dim3(blocks_for(n)), dim3(kCloudBlock), 0, (hipStream_t)stream, xyz, (long long)n,
-                       g, (long long*)keys);
-    return itermvs_launch_status();
+    return flat_launch<cloud_cell_keys_kernel, kCloudBlock>({n, kCloudMaxPoints}, (hipStream_t)stream, xyz, (long long)n, g, (long long*)keys);
 }
 
 extern "C" int itermvs_cloud_reduce_round(const float* xyz_sorted, const int64_t* keys_sorted, const int32_t* rank_sorted,
@@ -157,10 +155,8 @@ extern "C" int itermvs_cloud_reduce_round(const float* xyz_sorted, const int64_t
     ITERMVS_RETURN_IF(bad, bad);
     ITERMVS_RETURN_IF(!isfinite(dst) || !(dst > 0.0) || edge < dst, ITERMVS_ERR_DIMS);      // 27 cells must hold the radius
     const CloudGrid g{ox, oy, oz, edge, nx, ny, nz};
-    hipLaunchKernelGGL(cloud_reduce_round_kernel, dim3(blocks_for(n)), dim3(kCloudBlock), 0, (hipStream_t)stream, xyz_sorted,
-                       (const long long*)keys_sorted, (const int*)rank_sorted, (long long)n, g, dst * dst, (int*)state,
-                       (int*)undecided);
-    return itermvs_launch_status();
+    return flat_launch<cloud_reduce_round_kernel, kCloudBlock>({n, kCloudMaxPoints}, (hipStream_t)stream, xyz_sorted,
+        (const long long*)keys_sorted, (const int*)rank_sorted, (long long)n, g, dst * dst, (int*)state, (int*)undecided);
 }
 
 extern "C" int itermvs_cloud_nn_distance(const float* q_from, int64_t nq, const int64_t* index, int64_t n_index,
@@ -168,7 +164,7 @@ extern "C" int itermvs_cloud_nn_distance(const float* q_from, int64_t nq, const 
                                          double oz, int32_t nx, int32_t ny, int32_t nz, double edge, const double* region,
                                          double cap, int32_t rings, double* best_d2, uint8_t* done, double* dist, void* stream) {
     ITERMVS_RETURN_IF(!q_from || !to_sorted || !keys_sorted || !region || !best_d2 || !done || !dist, ITERMVS_ERR_NULL);
-    ITERMVS_RETURN_IF(nq < 1 || nq > 0x7fffff00LL || (index && (n_index < 1 || n_index > nq)), ITERMVS_ERR_DIMS);
+    ITERMVS_RETURN_IF(nq < 1 || nq > kCloudMaxPoints || (index && (n_index < 1 || n_index > nq)), ITERMVS_ERR_DIMS);
     const int bad = check_grid(nt, ox, oy, oz, nx, ny, nz, edge);
     ITERMVS_RETURN_IF(bad, bad);
     ITERMVS_RETURN_IF(!isfinite(cap) || !(cap > 0.0) || rings < 1 || rings > kMaxCellDim, ITERMVS_ERR_DIMS);
@@ -178,18 +174,16 @@ extern "C" int itermvs_cloud_nn_distance(const float* q_from, int64_t nq, const 
         reg.hi[a] = region[3 + a];
     }
     const CloudGrid g{ox, oy, oz, edge, nx, ny, nz};
-    hipLaunchKernelGGL(cloud_nn_distance_kernel, dim3(blocks_for(index ? n_index : nq)), dim3(kCloudBlock), 0,
-                       (hipStream_t)stream, q_from, (long long)nq, (const long long*)index, (long long)n_index, to_sorted,
-                       (const long long*)keys_sorted, (long long)nt, g, reg, cap, rings, best_d2, done, dist);
-    return itermvs_launch_status();
+    return flat_launch<cloud_nn_distance_kernel, kCloudBlock>({index ? n_index : nq, kCloudMaxPoints}, (hipStream_t)stream, q_from, (long long)nq,
+        (const long long*)index, (long long)n_index, to_sorted, (const long long*)keys_sorted, (long long)nt, g, reg, cap, rings, best_d2, done,
+        dist);
 }
 
 extern "C" int itermvs_cloud_in_mask(const float* xyz, int64_t n, const uint8_t* mask, int32_t sx, int32_t sy, int32_t sz,
                                      double bx, double by, double bz, double res, uint8_t* out, void* stream) {
     ITERMVS_RETURN_IF(!xyz || !mask || !out, ITERMVS_ERR_NULL);
-    ITERMVS_RETURN_IF(n < 1 || n > 0x7fffff00LL || sx < 1 || sy < 1 || sz < 1, ITERMVS_ERR_DIMS);
+    ITERMVS_RETURN_IF(n < 1 || n > kCloudMaxPoints || sx < 1 || sy < 1 || sz < 1, ITERMVS_ERR_DIMS);
     ITERMVS_RETURN_IF(!finite_all(bx, by, bz, res) || !(res > 0.0), ITERMVS_ERR_DIMS);
-    hipLaunchKernelGGL(cloud_in_mask_kernel, dim3(blocks_for(n)), dim3(kCloudBlock), 0, (hipStream_t)stream, xyz, (long long)n,
-                       mask, sx, sy, sz, bx, by, bz, res, out);
-    return itermvs_launch_status();
+    return flat_launch<cloud_in_mask_kernel, kCloudBlock>({n, kCloudMaxPoints}, (hipStream_t)stream, xyz, (long long)n, mask, sx, sy, sz, bx, by,
+        bz, res, out);
 }

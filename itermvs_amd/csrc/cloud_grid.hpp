@@ -13,11 +13,12 @@
 #pragma once
 #include <math.h>
 
-#include "common.hpp"
+#include "flat_launch.hpp"
 
 namespace itermvs {
 
 constexpr int kCloudBlock = 256;
+constexpr int64_t kCloudMaxPoints = 0x7fffff00LL;      // points of one launch (tighter than flat_launch.hpp's own limit)
 constexpr int kMaxCellDim = 1 << 21;                    // per axis: three axes fit a 63-bit key
 constexpr double kCellClamp = 4194304.0;                // 2^22: a query's cell far outside the grid, still safe in int arithmetic
 constexpr double kRingShrink = 1.0 - 1.0 / 1048576.0;   // ring lower bounds give way 2^-20 to the rounding of (p - origin) / edge
@@ -114,14 +115,10 @@ static inline bool finite_all(double a, double b, double c, double d) {
 
 // ITERMVS_OK or the error of a grid description; n is the number of points of the launch
 static inline int check_grid(long long n, double ox, double oy, double oz, int nx, int ny, int nz, double edge) {
-    ITERMVS_RETURN_IF(n < 1 || n > 0x7fffff00LL, ITERMVS_ERR_DIMS);
+    ITERMVS_RETURN_IF(n < 1 || n > kCloudMaxPoints, ITERMVS_ERR_DIMS);
     ITERMVS_RETURN_IF(!finite_all(ox, oy, oz, edge) || !(edge > 0.0), ITERMVS_ERR_DIMS);
     ITERMVS_RETURN_IF(nx < 1 || ny < 1 || nz < 1 || nx > kMaxCellDim || ny > kMaxCellDim || nz > kMaxCellDim, ITERMVS_ERR_DIMS);
     return ITERMVS_OK;
-}
-
-static inline unsigned blocks_for(long long n) {
-    return (unsigned)((n + kCloudBlock - 1) / kCloudBlock);
 }
 
 }  // namespace itermvs

@@ -260,7 +260,7 @@ using namespace itermvs;
 extern "C" int itermvs_cloud_crop(const float* xyz, int64_t n, const double* T, int32_t axis, double axis_min, double axis_max,
                                   const double* polygon, int32_t n_poly, double* poly_ws, uint8_t* out, void* stream) {
     ITERMVS_RETURN_IF(!xyz || !T || !polygon || !poly_ws || !out, ITERMVS_ERR_NULL);
-    ITERMVS_RETURN_IF(n < 1 || n > 0x7fffff00LL || axis < 0 || axis > 2 || n_poly < 3 || n_poly > kMaxPoly, ITERMVS_ERR_DIMS);
+    ITERMVS_RETURN_IF(n < 1 || n > kCloudMaxPoints || axis < 0 || axis > 2 || n_poly < 3 || n_poly > kMaxPoly, ITERMVS_ERR_DIMS);
     ITERMVS_RETURN_IF(isnan(axis_min) || isnan(axis_max), ITERMVS_ERR_DIMS);
     Transform tr;
     ITERMVS_RETURN_IF(!read_transform(T, tr), ITERMVS_ERR_DIMS);
@@ -276,26 +276,23 @@ extern "C" int itermvs_cloud_crop(const float* xyz, int64_t n, const double* T, 
         }
         hipLaunchKernelGGL(cloud_poly_upload_kernel, dim3(1), dim3(kPolyChunk), 0, (hipStream_t)stream, c, first, count, poly_ws);
     }
-    hipLaunchKernelGGL(cloud_crop_kernel, dim3(blocks_for(n)), dim3(kCloudBlock), 0, (hipStream_t)stream, xyz, (long long)n, tr,
-                       (int)axis, u, v, axis_min, axis_max, (const double*)poly_ws, (int)n_poly, out);
-    return itermvs_launch_status();
+    return flat_launch<cloud_crop_kernel, kCloudBlock>({n, kCloudMaxPoints}, (hipStream_t)stream, xyz, (long long)n, tr, (int)axis, u, v,
+        axis_min, axis_max, (const double*)poly_ws, (int)n_poly, out);
 }
 
 extern "C" int itermvs_cloud_voxel_heads(const int64_t* keys_sorted, int64_t n, int32_t* head, void* stream) {
     ITERMVS_RETURN_IF(!keys_sorted || !head, ITERMVS_ERR_NULL);
-    ITERMVS_RETURN_IF(n < 1 || n > 0x7fffff00LL, ITERMVS_ERR_DIMS);
-    hipLaunchKernelGGL(cloud_voxel_heads_kernel, dim3(blocks_for(n)), dim3(kCloudBlock), 0, (hipStream_t)stream,
-                       (const long long*)keys_sorted, (long long)n, (int*)head);
-    return itermvs_launch_status();
+    ITERMVS_RETURN_IF(n < 1 || n > kCloudMaxPoints, ITERMVS_ERR_DIMS);
+    return flat_launch<cloud_voxel_heads_kernel, kCloudBlock>({n, kCloudMaxPoints}, (hipStream_t)stream, (const long long*)keys_sorted,
+        (long long)n, (int*)head);
 }
 
 extern "C" int itermvs_cloud_voxel_mean(const float* xyz_sorted, const int64_t* keys_sorted, const int64_t* rank, int64_t n,
                                         int64_t n_out, float* out, void* stream) {
     ITERMVS_RETURN_IF(!xyz_sorted || !keys_sorted || !rank || !out, ITERMVS_ERR_NULL);
-    ITERMVS_RETURN_IF(n < 1 || n > 0x7fffff00LL || n_out < 1 || n_out > n, ITERMVS_ERR_DIMS);
-    hipLaunchKernelGGL(cloud_voxel_mean_kernel, dim3(blocks_for(n)), dim3(kCloudBlock), 0, (hipStream_t)stream, xyz_sorted,
-                       (const long long*)keys_sorted, (const long long*)rank, (long long)n, (long long)n_out, out);
-    return itermvs_launch_status();
+    ITERMVS_RETURN_IF(n < 1 || n > kCloudMaxPoints || n_out < 1 || n_out > n, ITERMVS_ERR_DIMS);
+    return flat_launch<cloud_voxel_mean_kernel, kCloudBlock>({n, kCloudMaxPoints}, (hipStream_t)stream, xyz_sorted, (const long long*)keys_sorted,
+        (const long long*)rank, (long long)n, (long long)n_out, out);
 }
 
 extern "C" int itermvs_cloud_nn_index(const float* q, int64_t nq, const double* T, const float* to_sorted,
@@ -303,28 +300,26 @@ extern "C" int itermvs_cloud_nn_index(const float* q, int64_t nq, const double* 
                                       int32_t nx, int32_t ny, int32_t nz, double edge, double max_dist, int32_t rings,
                                       int64_t* idx, double* d2, void* stream) {
     ITERMVS_RETURN_IF(!q || !T || !idx || !d2 || (nt > 0 && (!to_sorted || !keys_sorted || !perm)), ITERMVS_ERR_NULL);
-    ITERMVS_RETURN_IF(nq < 1 || nq > 0x7fffff00LL || nt < 0, ITERMVS_ERR_DIMS);
+    ITERMVS_RETURN_IF(nq < 1 || nq > kCloudMaxPoints || nt < 0, ITERMVS_ERR_DIMS);
     const int bad = check_grid(nt > 0 ? nt : 1, ox, oy, oz, nx, ny, nz, edge);
     ITERMVS_RETURN_IF(bad, bad);
     ITERMVS_RETURN_IF(!isfinite(max_dist) || !(max_dist > 0.0) || rings < 1 || rings > kMaxCellDim, ITERMVS_ERR_DIMS);
     Transform tr;
     ITERMVS_RETURN_IF(!read_transform(T, tr), ITERMVS_ERR_DIMS);
     const CloudGrid g{ox, oy, oz, edge, nx, ny, nz};
-    hipLaunchKernelGGL(cloud_nn_index_kernel, dim3(blocks_for(nq)), dim3(kCloudBlock), 0, (hipStream_t)stream, q, (long long)nq,
-                       tr, to_sorted, (const long long*)keys_sorted, (const long long*)perm, (long long)nt, g, max_dist,
-                       max_dist * max_dist, (int)rings, (long long*)idx, d2);
-    return itermvs_launch_status();
+    return flat_launch<cloud_nn_index_kernel, kCloudBlock>({nq, kCloudMaxPoints}, (hipStream_t)stream, q, (long long)nq, tr, to_sorted,
+        (const long long*)keys_sorted, (const long long*)perm, (long long)nt, g, max_dist, max_dist * max_dist, (int)rings, (long long*)idx, d2);
 }
 
 extern "C" int itermvs_cloud_umeyama_groups(int64_t n) {
-    ITERMVS_RETURN_IF(n < 1 || n > 0x7fffff00LL, ITERMVS_ERR_DIMS);
+    ITERMVS_RETURN_IF(n < 1 || n > kCloudMaxPoints, ITERMVS_ERR_DIMS);
     return umeyama_groups(n);
 }
 
 extern "C" int itermvs_cloud_umeyama_sums(const float* q, int64_t n, const double* T, const int64_t* idx, const double* d2,
                                           const float* target, int64_t nt, double* partials, double* sums, void* stream) {
     ITERMVS_RETURN_IF(!q || !T || !idx || !d2 || !partials || !sums || (nt > 0 && !target), ITERMVS_ERR_NULL);
-    ITERMVS_RETURN_IF(n < 1 || n > 0x7fffff00LL || nt < 0 || nt > 0x7fffff00LL, ITERMVS_ERR_DIMS);
+    ITERMVS_RETURN_IF(n < 1 || n > kCloudMaxPoints || nt < 0 || nt > kCloudMaxPoints, ITERMVS_ERR_DIMS);
     Transform tr;
     ITERMVS_RETURN_IF(!read_transform(T, tr), ITERMVS_ERR_DIMS);
     const int groups = umeyama_groups(n);

@@ -257,16 +257,8 @@ __device__ __forceinline__ float init_hypothesis(int n, int N, float inv_min, fl
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
-// F.interpolate(x, scale_factor=s, 'bilinear') for integer s, optional tanh: output element t of [M, H*s, W*s]
-// (bilinear_up_kernel, and the launches that carry it beside another piece of work)
-// `interleave` > 0: M = B * interleave maps, stored pixel-major [B, H*s, W*s, interleave] instead of planar
-__device__ __forceinline__ void bilinear_up_body(const float* __restrict__ x, int M, int H, int W, int scale, int act,
-                                                 float* __restrict__ out, int64_t t, int interleave = 0) {
-    const int OH = H * scale, OW = W * scale;
-    if (t >= (int64_t)M * OH * OW) return;
-    const int ox = (int)(t % OW);
-    const int oy = (int)((t / OW) % OH);
-    const int m = (int)(t / ((int64_t)OW * OH));
+// F.interpolate(x, scale_factor=s, 'bilinear') for integer s, optional tanh: output sample (oy, ox) of the map xm [H, W]
+__device__ __forceinline__ float bilinear_up_sample(const float* __restrict__ xm, int H, int W, int scale, int oy, int ox, int act) {
     const float rs = 1.0f / (float)scale;
     float sy = ((float)oy + 0.5f) * rs - 0.5f;
     float sx = ((float)ox + 0.5f) * rs - 0.5f;
@@ -278,11 +270,22 @@ __device__ __forceinline__ void bilinear_up_body(const float* __restrict__ x, in
     const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
     const float ly1 = sy - (float)y0, lx1 = sx - (float)x0;
     const float ly0 = 1.0f - ly1, lx0 = 1.0f - lx1;
-    const float* xm = x + (size_t)m * H * W;
     const float top = xm[(size_t)y0 * W + x0] * lx0 + xm[(size_t)y0 * W + x1] * lx1;
     const float bot = xm[(size_t)y1 * W + x0] * lx0 + xm[(size_t)y1 * W + x1] * lx1;
-    float v = top * ly0 + bot * ly1;
-    if (act == 1) v = tanhf(v);
+    const float v = top * ly0 + bot * ly1;
+    return act == 1 ? tanhf(v) : v;
+}
+
+// output element t of [M, H*s, W*s] (bilinear_up_kernel, and the launches that carry it beside another piece of work)
+// `interleave` > 0: M = B * interleave maps, stored pixel-major [B, H*s, W*s, interleave] instead of planar
+__device__ __forceinline__ void bilinear_up_body(const float* __restrict__ x, int M, int H, int W, int scale, int act,
+                                                 float* __restrict__ out, int64_t t, int interleave = 0) {
+    const int OH = H * scale, OW = W * scale;
+    if (t >= (int64_t)M * OH * OW) return;
+    const int ox = (int)(t % OW);
+    const int oy = (int)((t / OW) % OH);
+    const int m = (int)(t / ((int64_t)OW * OH));
+    const float v = bilinear_up_sample(x + (size_t)m * H * W, H, W, scale, oy, ox, act);
     if (interleave > 0) {
         const int bb = m / interleave, ss = m - bb * interleave;
         out[(((int64_t)bb * OH + oy) * OW + ox) * interleave + ss] = v;

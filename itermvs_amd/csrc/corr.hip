@@ -15,6 +15,7 @@
 //   Results are transposed through LDS so the [B,N,8,H,W] planes CorrNet / PixelViewWeight
 //   consume are written as full rows of TILE pixels.
 #include "corr_common.hpp"
+#include "flat_launch.hpp"
 
 namespace itermvs {
 
@@ -601,10 +602,8 @@ extern "C" int itermvs_tap_indices(const itermvs_tap_params* p, void* stream) {
     for (int n = 0; n < ITERMVS_MAX_HYP; ++n) a.offs[n] = p->offsets[n];
     a.inv_min = p->inv_depth_min; a.inv_max = p->inv_depth_max; a.out = p->out; a.coords = p->coords;
     a.B = p->B; a.S = p->S; a.H = p->H; a.W = p->W; a.N = p->N; a.H1 = p->H1; a.W1 = p->W1; a.init = p->init;
-    const int64_t total = (int64_t)p->B * p->S * p->N * p->H * p->W;
-    ITERMVS_RETURN_IF(total >= ((int64_t)1 << 31) * 256, ITERMVS_ERR_DIMS);
-    hipLaunchKernelGGL(tap_indices_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    return itermvs_launch_status();
+    // (the kernel keeps H * W in an int)
+    return flat_launch<tap_indices_kernel, 256>({flat_items({p->B, p->S, p->N, p->H, p->W}), kFlatInt32}, (hipStream_t)stream, a);
 }
 
 extern "C" int itermvs_pvw_tail(const float* x, const float* w, const float* bias, int32_t M, int32_t N, int32_t C,
@@ -612,11 +611,11 @@ extern "C" int itermvs_pvw_tail(const float* x, const float* w, const float* bia
     ITERMVS_RETURN_IF(!x || !w || !out, ITERMVS_ERR_NULL);
     ITERMVS_RETURN_IF(M < 1 || P < 1 || N < 1 || N > 32, ITERMVS_ERR_DIMS);
     ITERMVS_RETURN_IF(C != 16, ITERMVS_ERR_CHANNELS);
-    const dim3 grid((P + 63) / 64, M);
-    if (N <= 8) hipLaunchKernelGGL((pvw_tail_kernel<16, 1>), grid, dim3(512), 0, (hipStream_t)stream, x, w, bias, N, P, out);
-    else if (N <= 16) hipLaunchKernelGGL((pvw_tail_kernel<16, 2>), grid, dim3(512), 0, (hipStream_t)stream, x, w, bias, N, P, out);
-    else hipLaunchKernelGGL((pvw_tail_kernel<16, 4>), grid, dim3(512), 0, (hipStream_t)stream, x, w, bias, N, P, out);
-    return itermvs_launch_status();
+    const FlatItems n{(int64_t)8 * P, kFlatMaxWork, M};      // block = 64 pixels x 8 waves, grid.y = M
+    const hipStream_t st = (hipStream_t)stream;
+    if (N <= 8) return flat_launch<pvw_tail_kernel<16, 1>, 512>(n, st, x, w, bias, N, P, out);
+    if (N <= 16) return flat_launch<pvw_tail_kernel<16, 2>, 512>(n, st, x, w, bias, N, P, out);
+    return flat_launch<pvw_tail_kernel<16, 4>, 512>(n, st, x, w, bias, N, P, out);
 }
 
 // The four fused entry points: check (corr_common.hpp), fill the kernel arguments, launch.  The direct and the slot form of
@@ -791,16 +790,20 @@ extern "C" int itermvs_corr_init_slots(const itermvs_corr_init_params* p, const 
     return corr_init_entry(p, src, stream);
 }
 
+// the aggregation piece: a thread owns one output element, four of them (vec4), or a pixel's 8 groups (corr_layout 1); the kernel
+// keeps N * 8 (and itermvs_view_aggregate_up H3 * W3) in an int, so B * N * 8 * P stays below 2^31
+static FlatItems aggregate_items(int B, int N, int64_t P, int per_thread) {
+    return {flat_items({B, N, ITERMVS_GROUPS, P}) / per_thread, kFlatInt32 / per_thread};
+}
+
 extern "C" int itermvs_view_aggregate(const float* corr, const float* w, int32_t S, int32_t B, int32_t N, int32_t P,
                                       float* out, void* stream) {
     ITERMVS_RETURN_IF(!corr || !w || !out, ITERMVS_ERR_NULL);
     ITERMVS_RETURN_IF(S < 1 || B < 1 || N < 1 || P < 1, ITERMVS_ERR_DIMS);
     const int vec4 = (P & 3) == 0 && ((((uintptr_t)corr) | ((uintptr_t)w) | ((uintptr_t)out)) & 15) == 0;
-    const int64_t total = ((int64_t)B * N * ITERMVS_GROUPS * P) / (vec4 ? 4 : 1);
-    const int na = (int)((total + 255) / 256);
-    hipLaunchKernelGGL(view_aggregate_kernel, dim3((unsigned)na), dim3(256), 0, (hipStream_t)stream,
-                       corr, w, S, B, N * ITERMVS_GROUPS, P, out, na, 0, 0, (float*)nullptr, vec4, 0, 0);
-    return itermvs_launch_status();
+    return flat_launch<view_aggregate_kernel, 256>(aggregate_items(B, N, P, vec4 ? 4 : 1), (hipStream_t)stream, corr, w, S, B,
+                                                   N * ITERMVS_GROUPS, P, out, (int)kFlatInt32 /* every block aggregates */, 0, 0,
+                                                   (float*)nullptr, vec4, 0, 0);
 }
 
 extern "C" int itermvs_view_aggregate_up(const float* corr, int32_t corr_layout, const float* w, int32_t S, int32_t B, int32_t N, int32_t H3,
@@ -809,25 +812,21 @@ extern "C" int itermvs_view_aggregate_up(const float* corr, int32_t corr_layout,
     ITERMVS_RETURN_IF(S < 1 || B < 1 || N < 1 || H3 < 1 || W3 < 1, ITERMVS_ERR_DIMS);
     ITERMVS_RETURN_IF(corr_layout != 0 && corr_layout != 1, ITERMVS_ERR_LAYOUT);
     ITERMVS_RETURN_IF(corr_layout == 1 && ((uintptr_t)corr) % 16, ITERMVS_ERR_ALIGN);
-    const int P = H3 * W3;
+    const int64_t P = (int64_t)H3 * W3;
     const int vec4 = (P & 3) == 0 && ((((uintptr_t)corr) | ((uintptr_t)w) | ((uintptr_t)out)) & 15) == 0;
-    const int na = corr_layout == 1 ? (int)(((int64_t)B * N * P + 255) / 256)
-                                    : (int)(((int64_t)B * N * ITERMVS_GROUPS * P / (vec4 ? 4 : 1) + 255) / 256);
-    const int nu = (int)(((int64_t)B * S * P * 4 + 255) / 256);
-    hipLaunchKernelGGL(view_aggregate_kernel, dim3((unsigned)(na + nu)), dim3(256), 0, (hipStream_t)stream,
-                       corr, w, S, B, N * ITERMVS_GROUPS, P, out, na, H3, W3, w_up, vec4, w_up_interleaved ? 1 : 0, corr_layout);
-    return itermvs_launch_status();
+    FlatItems both;
+    int na;
+    const int rc = flat_pair(aggregate_items(B, N, P, corr_layout == 1 ? ITERMVS_GROUPS : vec4 ? 4 : 1), {flat_items({B, S, H3, W3, 4})}, 256,
+                             &both, &na);
+    ITERMVS_RETURN_IF(rc != ITERMVS_OK, rc);
+    return flat_launch<view_aggregate_kernel, 256>(both, (hipStream_t)stream, corr, w, S, B, N * ITERMVS_GROUPS, (int)P, out, na, H3, W3, w_up,
+                                                   vec4, w_up_interleaved ? 1 : 0, corr_layout);
 }
 
 extern "C" int itermvs_softmax_max(const float* x, int32_t M, int32_t N, int32_t P, float* out, void* stream) {
     ITERMVS_RETURN_IF(!x || !out, ITERMVS_ERR_NULL);
     ITERMVS_RETURN_IF(M < 1 || N < 1 || P < 1, ITERMVS_ERR_DIMS);
-    const int64_t total = (int64_t)M * P;
     if (N <= 32)    // 64-thread blocks: the M * P pixels spread over as many CUs as possible
-        hipLaunchKernelGGL(softmax_max_small_kernel<32>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, (hipStream_t)stream, x,
-                           M, N, P, out);
-    else
-        hipLaunchKernelGGL(softmax_max_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, M,
-                           N, P, out);
-    return itermvs_launch_status();
+        return flat_launch<softmax_max_small_kernel<32>, 64>({flat_items({M, P})}, (hipStream_t)stream, x, M, N, P, out);
+    return flat_launch<softmax_max_kernel, 256>({flat_items({M, P})}, (hipStream_t)stream, x, M, N, P, out);
 }

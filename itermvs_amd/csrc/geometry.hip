@@ -1,6 +1,7 @@
 // Camera composition, the plain (un-fused) warp seam and reference-feature resampling.
 #include "corr_common.hpp"
 #include "compose.hpp"
+#include "flat_launch.hpp"
 
 namespace itermvs {
 
@@ -171,11 +172,9 @@ extern "C" int itermvs_compose_proj(const float* mats, int32_t n_sets, int32_t V
     ITERMVS_RETURN_IF(inv_min && (!depth_min || !depth_max || !inv_max || B < 1), ITERMVS_ERR_NULL);
     ITERMVS_RETURN_IF(n_sets < 1, ITERMVS_ERR_DIMS);
     ITERMVS_RETURN_IF(V < 2 || V - 1 > ITERMVS_MAX_SRC, ITERMVS_ERR_VIEWS);
-    int total = n_sets * (V - 1);
-    if (inv_min && B > total) total = B;
     const ComposeArgs c{mats, out, nan_flag, depth_min, depth_max, inv_min, inv_max, n_sets, V, B};
-    hipLaunchKernelGGL(compose_proj_kernel, dim3((total + 63) / 64), dim3(64), 0, (hipStream_t)stream, c);
-    return itermvs_launch_status();
+    const int64_t total = flat_items({n_sets, V - 1});                // compose_proj_body takes the item and n_sets * (V - 1) as ints
+    return flat_launch<compose_proj_kernel, 64>({inv_min && B > total ? B : total, kFlatInt32}, (hipStream_t)stream, c);
 }
 
 extern "C" int itermvs_warp(const itermvs_fmap* src, const float* proj, const float* depth, int32_t B, int32_t N,
@@ -183,10 +182,7 @@ extern "C" int itermvs_warp(const itermvs_fmap* src, const float* proj, const fl
     ITERMVS_RETURN_IF(src && src->dtype != ITERMVS_F32, ITERMVS_ERR_DTYPE);
     ITERMVS_RETURN_IF(!src || !src->data || !proj || !depth || !out, ITERMVS_ERR_NULL);
     ITERMVS_RETURN_IF(B < 1 || N < 1 || H < 1 || W < 1 || src->C < 1 || src->H < 1 || src->W < 1, ITERMVS_ERR_DIMS);
-    const int64_t total = (int64_t)B * N * H * W;
-    hipLaunchKernelGGL(warp_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *src, proj,
-                       depth, B, N, H, W, out, mask);
-    return itermvs_launch_status();
+    return flat_launch<warp_kernel, 256>({flat_items({B, N, H, W})}, (hipStream_t)stream, *src, proj, depth, B, N, H, W, out, mask);
 }
 
 extern "C" int itermvs_warp_backward(const float* grad_out, const float* proj, const float* depth, int32_t B, int32_t C,
@@ -194,10 +190,9 @@ extern "C" int itermvs_warp_backward(const float* grad_out, const float* proj, c
                                      void* stream) {
     ITERMVS_RETURN_IF(!grad_out || !proj || !depth || !grad_src, ITERMVS_ERR_NULL);
     ITERMVS_RETURN_IF(B < 1 || C < 1 || N < 1 || H < 1 || W < 1 || H1 < 1 || W1 < 1, ITERMVS_ERR_DIMS);
-    const int64_t total = (int64_t)B * N * H * W;
-    hipLaunchKernelGGL(warp_backward_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       grad_out, proj, depth, B, C, N, H, W, H1, W1, grad_src);
-    return itermvs_launch_status();
+    ITERMVS_RETURN_IF((int64_t)H1 * W1 > kFlatInt32, ITERMVS_ERR_DIMS);      // the kernel forms y * W1 + x of the source map in an int
+    return flat_launch<warp_backward_kernel, 256>({flat_items({B, N, H, W})}, (hipStream_t)stream, grad_out, proj, depth, B, C, N, H, W, H1,
+                                                  W1, grad_src);
 }
 
 static int launch_ref_quarter(const itermvs_fmap* r1, const itermvs_fmap* r2, const itermvs_fmap* r3, int32_t B, float* out,

@@ -10,7 +10,7 @@
 // cv2 is not in this image: the resize follows the published algorithm (parity unpinned for this stage, like the filter).
 // Uploading the uint8 image (5.8 MB for a 1600 x 1200 DTU view) instead of the float32 pyramid (29.5 MB) also cuts the
 // host-to-device traffic of a depth map five-fold.
-#include "common.hpp"
+#include "flat_launch.hpp"
 #include "image_level0.hpp"
 
 namespace itermvs {
@@ -38,9 +38,7 @@ __global__ void image_down_kernel(const float* __restrict__ l0, int M, int H, in
 }
 
 int image_pyramid_down(const float* level0, int M, int H, int W, int lvl, float* out, hipStream_t stream) {
-    const int64_t n = (int64_t)M * (H >> lvl) * (W >> lvl);
-    hipLaunchKernelGGL(image_down_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, level0, M, H, W, lvl, out);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    return flat_launch<image_down_kernel, 256>({flat_items({M, H >> lvl, W >> lvl})}, stream, level0, M, H, W, lvl, out);
 }
 
 }  // namespace itermvs
@@ -52,15 +50,10 @@ extern "C" int itermvs_image_pyramid(const uint8_t* src, int32_t V, int32_t Hs, 
     ITERMVS_RETURN_IF(!src || !level0, ITERMVS_ERR_NULL);
     ITERMVS_RETURN_IF(V < 1 || Hs < 1 || Ws < 1 || H < 1 || W < 1, ITERMVS_ERR_DIMS);
     ITERMVS_RETURN_IF((level1 || level2 || level3) && ((H | W) & 7), ITERMVS_ERR_DIMS);
-    const int64_t n0 = (int64_t)V * H * W;
-    hipLaunchKernelGGL(image_level0_kernel, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, V, Hs,
-                       Ws, H, W, level0);
+    ITERMVS_RETURN_IF(Ws > kFlatInt32 / 3, ITERMVS_ERR_DIMS);            // level0_pixel forms x * 3 + c of a source row in an int
+    int rc = flat_launch<image_level0_kernel, 256>({flat_items({V, H, W})}, (hipStream_t)stream, src, V, Hs, Ws, H, W, level0);
     float* lv[3] = {level1, level2, level3};
-    for (int l = 1; l <= 3; ++l) {
-        if (!lv[l - 1]) continue;
-        const int64_t n = (int64_t)V * 3 * (H >> l) * (W >> l);
-        hipLaunchKernelGGL(image_down_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, level0,
-                           V * 3, H, W, l, lv[l - 1]);
-    }
-    return itermvs_launch_status();
+    for (int l = 1; l <= 3 && rc == ITERMVS_OK; ++l)
+        if (lv[l - 1]) rc = image_pyramid_down(level0, V * 3, H, W, l, lv[l - 1], (hipStream_t)stream);
+    return rc;
 }

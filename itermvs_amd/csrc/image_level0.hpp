@@ -41,7 +41,7 @@ __device__ __forceinline__ void level0_pixel(const uint8_t* __restrict__ src, in
     }
 }
 
-// enqueue image.hip's level-l kernel (l = 1..3) over level 0 [M,H,W] -> out [M,H>>l,W>>l]; 0 = launched
+// enqueue image.hip's level-l kernel (l = 1..3) over level 0 [M,H,W] -> out [M,H>>l,W>>l]; returns an ITERMVS_* status
 int image_pyramid_down(const float* level0, int M, int H, int W, int lvl, float* out, hipStream_t stream);
 
 }  // namespace itermvs

@@ -12,7 +12,7 @@
 // 1600 x 1200 -> anything smaller, 1 x 3 for 1200 -> 1152 rows).  Four neighbouring pixels per thread make the store
 // 12 contiguous bytes (three dwords) when the rows allow it; when the width is also kept, the 12 source bytes of each vertical
 // tap are three dword loads.  Otherwise one pixel per thread with byte accesses.
-#include "common.hpp"
+#include "flat_launch.hpp"
 
 namespace itermvs {
 
@@ -113,19 +113,13 @@ extern "C" int itermvs_resize_rgb8(const uint8_t* src, int32_t V, int32_t Hs, in
                                    const int32_t* yk, int32_t KY, uint8_t* out, void* stream) {
     ITERMVS_RETURN_IF(!src || !out || !xbounds || !xk || !ybounds || !yk, ITERMVS_ERR_NULL);
     ITERMVS_RETURN_IF(V < 1 || Hs < 1 || Ws < 1 || H < 1 || W < 1 || KX < 1 || KY < 1, ITERMVS_ERR_DIMS);
+    ITERMVS_RETURN_IF(H > kFlatInt32 / 2 || W > kFlatInt32 / 2, ITERMVS_ERR_DIMS);      // the kernel forms 2 * y and 2 * x in an int
     const bool wide = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(out) % 4 == 0);
     const bool same_w = wide && Ws == W && KX == 1 && (reinterpret_cast<uintptr_t>(src) % 4 == 0);
-    const int64_t n = (int64_t)V * H * (wide ? W / 4 : W);
-    const int64_t blocks = (n + kResizeBlock - 1) / kResizeBlock;
-    ITERMVS_RETURN_IF(blocks > 0x7fffffff, ITERMVS_ERR_DIMS);
+    const FlatItems n{flat_items({V, H, wide ? W / 4 : W})};
     const ResizeTables tb{xbounds, xk, ybounds, yk, KX, KY};
-    const dim3 grid((unsigned)blocks), block(kResizeBlock);
-    hipStream_t s = (hipStream_t)stream;
-    if (same_w)
-        hipLaunchKernelGGL((resize_rgb8_kernel<4, true>), grid, block, 0, s, src, V, Hs, Ws, H, W, tb, out);
-    else if (wide)
-        hipLaunchKernelGGL((resize_rgb8_kernel<4, false>), grid, block, 0, s, src, V, Hs, Ws, H, W, tb, out);
-    else
-        hipLaunchKernelGGL((resize_rgb8_kernel<1, false>), grid, block, 0, s, src, V, Hs, Ws, H, W, tb, out);
-    return itermvs_launch_status();
+    const hipStream_t s = (hipStream_t)stream;
+    if (same_w) return flat_launch<resize_rgb8_kernel<4, true>, kResizeBlock>(n, s, src, V, Hs, Ws, H, W, tb, out);
+    if (wide) return flat_launch<resize_rgb8_kernel<4, false>, kResizeBlock>(n, s, src, V, Hs, Ws, H, W, tb, out);
+    return flat_launch<resize_rgb8_kernel<1, false>, kResizeBlock>(n, s, src, V, Hs, Ws, H, W, tb, out);
 }

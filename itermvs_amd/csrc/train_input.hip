@@ -12,7 +12,7 @@
 //      src = min(floor(dst_index * (1.0 / ((double)dst / src))), src - 1)      per axis (OpenCV's published resizeNN)
 //    composed per recipe, with the PFM's bottom-up row order absorbed into the map.  cv2 is not in this image: the map is
 //    restated from OpenCV's source (unpinned, like image.hip's bilinear resize).
-#include "common.hpp"
+#include "flat_launch.hpp"
 #include "image_level0.hpp"
 
 namespace itermvs {
@@ -152,23 +152,22 @@ extern "C" int itermvs_image_pyramid_jitter(const uint8_t* src, int32_t V, int32
     ITERMVS_RETURN_IF(!src || !jitter || !lsum || !level0, ITERMVS_ERR_NULL);
     ITERMVS_RETURN_IF(V < 1 || V > 65535 || Hs < 1 || Ws < 1 || H < 1 || W < 1, ITERMVS_ERR_DIMS);
     ITERMVS_RETURN_IF((level1 || level2 || level3) && ((H | W) & 7), ITERMVS_ERR_DIMS);
+    ITERMVS_RETURN_IF(Ws > kFlatInt32 / 3, ITERMVS_ERR_DIMS);            // level0_pixel forms x * 3 + c of a source row in an int
+    // both grids before the first HIP call: level 0 with the view in grid.y, the levels below (fewer items than V * H * W) without
+    const FlatItems n0{flat_items({H, W}), kFlatMaxWork, V};
+    dim3 unused;
+    ITERMVS_RETURN_IF(flat_grid(n0, 256, &unused) || flat_grid({flat_items({V, H, W})}, 256, &unused), ITERMVS_ERR_DIMS);
     const hipStream_t st = (hipStream_t)stream;
     const int64_t npix = (int64_t)Hs * Ws;
     if (hipMemsetAsync(lsum, 0, sizeof(uint64_t) * (size_t)V, st) != hipSuccess) return ITERMVS_ERR_LAUNCH;
     const int64_t lb = (npix + 255) / 256;
     hipLaunchKernelGGL(jitter_lsum_kernel, dim3((unsigned)(lb < 64 ? lb : 64), (unsigned)V), dim3(256), 0, st, src, npix, jitter,
                        (unsigned long long*)lsum);
-    const int64_t n0 = (int64_t)H * W;
-    hipLaunchKernelGGL(image_level0_jitter_kernel, dim3((unsigned)((n0 + 255) / 256), (unsigned)V), dim3(256), 0, st, src, Hs, Ws,
-                       H, W, jitter, (const unsigned long long*)lsum, level0);
-    const int rc = itermvs_launch_status();
-    if (rc) return rc;
+    int rc = flat_launch<image_level0_jitter_kernel, 256>(n0, st, src, Hs, Ws, H, W, jitter, (const unsigned long long*)lsum, level0);
     float* lv[3] = {level1, level2, level3};
-    for (int l = 1; l <= 3; ++l) {
-        if (!lv[l - 1]) continue;
-        ITERMVS_RETURN_IF(image_pyramid_down(level0, V * 3, H, W, l, lv[l - 1], st), ITERMVS_ERR_LAUNCH);
-    }
-    return ITERMVS_OK;
+    for (int l = 1; l <= 3 && rc == ITERMVS_OK; ++l)
+        if (lv[l - 1]) rc = image_pyramid_down(level0, V * 3, H, W, l, lv[l - 1], st);
+    return rc;
 }
 
 extern "C" int itermvs_gt_pyramid(const float* depth_rows, const uint8_t* mask_src, const float* params, int32_t B, int32_t Hs,
@@ -184,7 +183,5 @@ extern "C" int itermvs_gt_pyramid(const float* depth_rows, const uint8_t* mask_s
     GtLevels o = {{depth0, depth1, depth2, depth3}, {mask0, mask1, mask2, mask3}};
     int64_t n = 0;
     for (int l = 0; l < 4; ++l) n += (int64_t)(H >> l) * (W >> l);
-    hipLaunchKernelGGL(gt_pyramid_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream,
-                       depth_rows, mask_src, params, Hs, Ws, H, W, recipe, o);
-    return itermvs_launch_status();
+    return flat_launch<gt_pyramid_kernel, 256>({n, kFlatMaxWork, B}, (hipStream_t)stream, depth_rows, mask_src, params, Hs, Ws, H, W, recipe, o);
 }

@@ -10,7 +10,7 @@
 //
 // Safety: the integer tap indices are formed only after `sx >= 0 && sx <= Ws - 1 && sy >= 0 && sy <= Hs - 1` held, which NaN
 // and +-Inf fail, so no parameter set makes the kernel read outside src.
-#include "common.hpp"
+#include "flat_launch.hpp"
 
 namespace itermvs {
 
@@ -175,9 +175,7 @@ extern "C" int itermvs_undistort_rgb8(const uint8_t* src, int32_t Hs, int32_t Ws
     ITERMVS_RETURN_IF(count < 0, ITERMVS_ERR_MODEL);
     ITERMVS_RETURN_IF(Hs < 1 || Ws < 1 || Ho < 1 || Wo < 1 || n_params != count, ITERMVS_ERR_DIMS);
     const bool wide = (Wo % 4 == 0) && (reinterpret_cast<uintptr_t>(out) % 4 == 0);
-    const int64_t n = (int64_t)Ho * (wide ? Wo / 4 : Wo);
-    const int64_t blocks = (n + kUndistortBlock - 1) / kUndistortBlock;
-    ITERMVS_RETURN_IF(blocks > 0x7fffffff, ITERMVS_ERR_DIMS);
+    const FlatItems n{flat_items({Ho, wide ? Wo / 4 : Wo})};
     UndistortArgs a{};
     a.src = src;
     a.out = out;
@@ -200,11 +198,6 @@ extern "C" int itermvs_undistort_rgb8(const uint8_t* src, int32_t Hs, int32_t Ws
     a.Ws = Ws;
     a.Ho = Ho;
     a.Wo = Wo;
-    const dim3 grid((unsigned)blocks), block(kUndistortBlock);
-    hipStream_t s = (hipStream_t)stream;
-    if (wide)
-        hipLaunchKernelGGL((undistort_rgb8_kernel<4>), grid, block, 0, s, a);
-    else
-        hipLaunchKernelGGL((undistort_rgb8_kernel<1>), grid, block, 0, s, a);
-    return itermvs_launch_status();
+    if (wide) return flat_launch<undistort_rgb8_kernel<4>, kUndistortBlock>(n, (hipStream_t)stream, a);
+    return flat_launch<undistort_rgb8_kernel<1>, kUndistortBlock>(n, (hipStream_t)stream, a);
 }

@@ -2,7 +2,7 @@
 // regression (models/itermvs.py:171-190, 201-219), ConvGRU gate math (models/module.py:59-66),
 // convex x4 up-sampling (models/module.py:127-140 + itermvs.py:262-264) and integer-factor
 // bilinear up-sampling (F.interpolate, align_corners=False).
-#include "common.hpp"
+#include "flat_launch.hpp"
 
 namespace itermvs {
 
@@ -241,22 +241,7 @@ __global__ void bilinear_up2_kernel(const float* __restrict__ x, int B, int C, i
     const int ox = (int)(r % OW);
     const int oy = (int)((r / OW) % OH);
     const int c = (int)(r / ((int64_t)OW * OH));
-    const float rs = 1.0f / (float)scale;
-    float sy = ((float)oy + 0.5f) * rs - 0.5f;
-    float sx = ((float)ox + 0.5f) * rs - 0.5f;
-    sy = sy < 0.0f ? 0.0f : sy;
-    sx = sx < 0.0f ? 0.0f : sx;
-    int y0 = (int)sy, x0 = (int)sx;
-    y0 = y0 > H - 1 ? H - 1 : y0;
-    x0 = x0 > W - 1 ? W - 1 : x0;
-    const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
-    const float ly1 = sy - (float)y0, lx1 = sx - (float)x0;
-    const float ly0 = 1.0f - ly1, lx0 = 1.0f - lx1;
-    const float* xm = x + ((size_t)b * C + c) * H * W;
-    const float top = xm[(size_t)y0 * W + x0] * lx0 + xm[(size_t)y0 * W + x1] * lx1;
-    const float bot = xm[(size_t)y1 * W + x0] * lx0 + xm[(size_t)y1 * W + x1] * lx1;
-    float v = top * ly0 + bot * ly1;
-    if (act == 1) v = tanhf(v);
+    const float v = bilinear_up_sample(x + ((size_t)b * C + c) * H * W, H, W, scale, oy, ox, act);
     out[b * out_sb + r] = v;
     if (out2) out2[b * out2_sb + r] = v;
 }
@@ -269,88 +254,82 @@ extern "C" int itermvs_bilinear_up2(const float* x, int32_t B, int32_t C, int32_
                                     float* out, int64_t out_sb, float* out2, int64_t out2_sb, void* stream) {
     ITERMVS_RETURN_IF(!x || !out, ITERMVS_ERR_NULL);
     ITERMVS_RETURN_IF(B < 1 || C < 1 || H < 1 || W < 1 || scale < 1, ITERMVS_ERR_DIMS);
-    const int64_t total = (int64_t)B * C * H * W * scale * scale;
-    hipLaunchKernelGGL(bilinear_up2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x,
-                       B, C, H, W, scale, act, out, out_sb, out2, out2_sb);
-    return itermvs_launch_status();
+    return flat_launch<bilinear_up2_kernel, 256>({flat_items({B, C, H, W, scale, scale})}, (hipStream_t)stream, x, B, C, H, W,
+                                                 scale, act, out, out_sb, out2, out2_sb);
 }
 
+// block = 32 pixels x 8 bin groups and grid.y = B: 8 * P items
 extern "C" int itermvs_prob_regress(const float* logits, int64_t sb, int64_t sc, int64_t sp, int32_t B, int32_t P,
                                     float* nd_out0, int64_t nd_sb0, float* nd_out1, int64_t nd_sb1, float* prob,
                                     int64_t* best, void* stream) {
     ITERMVS_RETURN_IF(!logits, ITERMVS_ERR_NULL);
     ITERMVS_RETURN_IF(B < 1 || P < 1, ITERMVS_ERR_DIMS);
-    hipLaunchKernelGGL(prob_regress_kernel, dim3((P + kTP - 1) / kTP, B), dim3(256), 0, (hipStream_t)stream, logits, sb,
-                       sc, sp, P, nd_out0, nd_sb0, nd_out1, nd_sb1, prob, best);
-    return itermvs_launch_status();
+    return flat_launch<prob_regress_kernel, 256>({(int64_t)kGroups * P, kFlatMaxWork, B}, (hipStream_t)stream, logits, sb, sc, sp, P, nd_out0,
+                                                 nd_sb0, nd_out1, nd_sb1, prob, best);
 }
 
 extern "C" int itermvs_gru_rh(const float* zr, const float* h, int64_t h_sb, float* rh, int64_t rh_sb, int32_t B,
                               int32_t hid, int32_t P, void* stream) {
     ITERMVS_RETURN_IF(!zr || !h || !rh, ITERMVS_ERR_NULL);
     ITERMVS_RETURN_IF(B < 1 || hid < 1 || P < 1, ITERMVS_ERR_DIMS);
-    const int64_t total = (int64_t)B * hid * P;
-    hipLaunchKernelGGL(gru_rh_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, zr, h,
-                       h_sb, rh, rh_sb, B, hid, P);
-    return itermvs_launch_status();
+    return flat_launch<gru_rh_kernel, 256>({flat_items({B, hid, P})}, (hipStream_t)stream, zr, h, h_sb, rh, rh_sb, B, hid, P);
 }
 
 extern "C" int itermvs_gru_out(const float* zr, const float* q, float* h, int64_t h_sb, float* h_copy, int32_t B,
                                int32_t hid, int32_t P, void* stream) {
     ITERMVS_RETURN_IF(!zr || !q || !h, ITERMVS_ERR_NULL);
     ITERMVS_RETURN_IF(B < 1 || hid < 1 || P < 1, ITERMVS_ERR_DIMS);
-    const int64_t total = (int64_t)B * hid * P;
-    hipLaunchKernelGGL(gru_out_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, zr, q,
-                       h, h_sb, h_copy, B, hid, P);
-    return itermvs_launch_status();
+    return flat_launch<gru_out_kernel, 256>({flat_items({B, hid, P})}, (hipStream_t)stream, zr, q, h, h_sb, h_copy, B, hid, P);
 }
 
 extern "C" int itermvs_pack_scores(const float* s0, const float* s1, const float* s2, const int32_t N[3], int32_t B,
                                    int32_t P, float* dst0, float* dst1, int64_t dst_sb, int32_t ch0, void* stream) {
     ITERMVS_RETURN_IF(!s0 || !s1 || !s2 || !N || (!dst0 && !dst1), ITERMVS_ERR_NULL);
     ITERMVS_RETURN_IF(B < 1 || P < 1 || N[0] < 1 || N[1] < 1 || N[2] < 1, ITERMVS_ERR_DIMS);
-    const int64_t total = (int64_t)B * (N[0] + N[1] + N[2]) * P;
-    hipLaunchKernelGGL(pack_scores_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, s0,
-                       s1, s2, N[0], N[1], N[2], B, P, dst0, dst1, dst_sb, ch0);
-    return itermvs_launch_status();
+    return flat_launch<pack_scores_kernel, 256>({flat_items({B, (int64_t)N[0] + N[1] + N[2], P}), kFlatInt32}, (hipStream_t)stream, s0, s1, s2,
+                                                N[0], N[1], N[2], B, P, dst0, dst1, dst_sb, ch0);
+}
+
+// what itermvs_convex_upsample and itermvs_final_upsample check alike, and the convex piece of their grid
+static int convex_items(const float* logits, const float* nd, const float* inv_depth_min, const float* inv_depth_max, int32_t B, int32_t H,
+                        int32_t W, const float* depth, const float* norm_out, FlatItems* convex) {
+    ITERMVS_RETURN_IF(!logits || !nd || !inv_depth_min || !inv_depth_max || !depth, ITERMVS_ERR_NULL);
+    ITERMVS_RETURN_IF(B < 1 || H < 1 || W < 1, ITERMVS_ERR_DIMS);
+    ITERMVS_RETURN_IF(((uintptr_t)depth) % 16 || ((uintptr_t)norm_out) % 16, ITERMVS_ERR_ALIGN);
+    *convex = {flat_items({B, H, 4, W}), kFlatInt32};      // the kernel forms the output row 4 * y + i in an int
+    return ITERMVS_OK;
 }
 
 extern "C" int itermvs_convex_upsample(const float* logits, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
                                        const float* nd, int64_t nd_sb, const float* inv_depth_min,
                                        const float* inv_depth_max, int32_t B, int32_t H, int32_t W, float* depth,
                                        float* norm_out, void* stream) {
-    ITERMVS_RETURN_IF(!logits || !nd || !inv_depth_min || !inv_depth_max || !depth, ITERMVS_ERR_NULL);
-    ITERMVS_RETURN_IF(B < 1 || H < 1 || W < 1, ITERMVS_ERR_DIMS);
-    ITERMVS_RETURN_IF(((uintptr_t)depth) % 16 || ((uintptr_t)norm_out) % 16, ITERMVS_ERR_ALIGN);
-    const int64_t total = (int64_t)B * H * 4 * W;
-    const int nc = (int)((total + 255) / 256);
-    hipLaunchKernelGGL(convex_upsample_kernel, dim3((unsigned)nc), dim3(256), 0, (hipStream_t)stream,
-                       logits, sb, sc, sy, sx, nd, nd_sb, inv_depth_min, inv_depth_max, B, H, W, depth, norm_out, nc,
-                       (const float*)nullptr, 0, 1, (float*)nullptr);
-    return itermvs_launch_status();
+    FlatItems convex;
+    const int rc = convex_items(logits, nd, inv_depth_min, inv_depth_max, B, H, W, depth, norm_out, &convex);
+    ITERMVS_RETURN_IF(rc != ITERMVS_OK, rc);
+    return flat_launch<convex_upsample_kernel, 256>(convex, (hipStream_t)stream, logits, sb, sc, sy, sx, nd, nd_sb, inv_depth_min, inv_depth_max,
+                                                    B, H, W, depth, norm_out, (int)kFlatInt32 /* every block is convex */, (const float*)nullptr, 0, 1,
+                                                    (float*)nullptr);
 }
 
 extern "C" int itermvs_final_upsample(const float* logits, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
                                       const float* nd, int64_t nd_sb, const float* inv_depth_min,
                                       const float* inv_depth_max, int32_t B, int32_t H, int32_t W, float* depth,
                                       const float* conf, int32_t M, float* conf_up, void* stream) {
-    ITERMVS_RETURN_IF(!logits || !nd || !inv_depth_min || !inv_depth_max || !depth || !conf || !conf_up, ITERMVS_ERR_NULL);
-    ITERMVS_RETURN_IF(B < 1 || H < 1 || W < 1 || M < 1, ITERMVS_ERR_DIMS);
-    ITERMVS_RETURN_IF(((uintptr_t)depth) % 16, ITERMVS_ERR_ALIGN);
-    const int nc = (int)(((int64_t)B * H * 4 * W + 255) / 256);
-    const int nb = (int)(((int64_t)M * H * W * 16 + 255) / 256);
-    hipLaunchKernelGGL(convex_upsample_kernel, dim3((unsigned)(nc + nb)), dim3(256), 0, (hipStream_t)stream,
-                       logits, sb, sc, sy, sx, nd, nd_sb, inv_depth_min, inv_depth_max, B, H, W, depth, (float*)nullptr, nc,
-                       conf, M, 4, conf_up);
-    return itermvs_launch_status();
+    ITERMVS_RETURN_IF(!conf || !conf_up, ITERMVS_ERR_NULL);
+    ITERMVS_RETURN_IF(M < 1, ITERMVS_ERR_DIMS);
+    FlatItems convex, both;
+    int nc, rc = convex_items(logits, nd, inv_depth_min, inv_depth_max, B, H, W, depth, nullptr, &convex);
+    if (rc == ITERMVS_OK) rc = flat_pair(convex, {flat_items({M, H, W, 16})}, 256, &both, &nc);
+    ITERMVS_RETURN_IF(rc != ITERMVS_OK, rc);
+    return flat_launch<convex_upsample_kernel, 256>(both, (hipStream_t)stream, logits, sb, sc, sy, sx, nd, nd_sb, inv_depth_min, inv_depth_max,
+                                                    B, H, W, depth, (float*)nullptr, nc, conf, M, 4, conf_up);
 }
 
 extern "C" int itermvs_bilinear_up(const float* x, int32_t M, int32_t H, int32_t W, int32_t scale, int32_t act,
                                    float* out, void* stream) {
     ITERMVS_RETURN_IF(!x || !out, ITERMVS_ERR_NULL);
     ITERMVS_RETURN_IF(M < 1 || H < 1 || W < 1 || scale < 1, ITERMVS_ERR_DIMS);
-    const int64_t total = (int64_t)M * H * W * scale * scale;
-    hipLaunchKernelGGL(bilinear_up_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x,
-                       M, H, W, scale, act, out);
-    return itermvs_launch_status();
+    return flat_launch<bilinear_up_kernel, 256>({flat_items({M, H, W, scale, scale})}, (hipStream_t)stream, x, M, H, W, scale, act,
+                                                out);
 }
