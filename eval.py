@@ -102,6 +102,30 @@ def build_parser() -> argparse.ArgumentParser:
                         "lies across a depth edge and is not used for the normal.  The default is the step --geo_depth_thres "
                         "already treats as another surface (at 640 px wide it still admits surfaces slanted by about 85 degrees); "
                         "a choice, not a measured optimum")
+    p.add_argument("--mesh", action="store_true",
+                   help="--filter with the point cloud assembled on the GPU (--fuse_points device or --fuse_source memory): also write "
+                        "<outdir>/<scan>_mesh.ply, a coloured triangle mesh.  Every reference view's fused depth map is integrated into "
+                        "a dense truncated-signed-distance volume on the GPU (itermvs_tsdf_integrate) and marching tetrahedra turns it "
+                        "into triangles (itermvs_tsdf_mesh); the same inputs give the same bytes.  Off (default): every byte as before")
+    p.add_argument("--mesh_resolution", type=int, default=256,
+                   help="--mesh: voxels along the longest side of the bounds (ignored with --mesh_voxel).  The default is a choice: "
+                        "a 256-cube of 12-byte voxels takes 0.2 GB, 512 takes 1.6 GB, plus as much again while the triangles are extracted")
+    p.add_argument("--mesh_voxel", type=float, default=None, help="--mesh: the voxel's side in world units, instead of --mesh_resolution")
+    p.add_argument("--mesh_bounds", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
+                   help="--mesh: the volume in world units, used as given.  Default: per axis the --mesh_bounds_quantile and 1 - quantile "
+                        "order statistics of the fused cloud's vertices, widened by the truncation distance")
+    p.add_argument("--mesh_bounds_quantile", type=float, default=0.01,
+                   help="--mesh without --mesh_bounds: share of the cloud's vertices left outside the volume at either end of each "
+                        "axis, in [0, 0.5).  The default keeps a few stray points from inflating the volume; a choice, not a measured optimum")
+    p.add_argument("--mesh_trunc", type=float, default=3.0,
+                   help="--mesh: truncation distance of the signed distance in voxels, at least 1.  The default spans the depth noise "
+                        "of a few voxels without bridging thin gaps; a choice, not a measured optimum")
+    p.add_argument("--mesh_min_count", type=int, default=2,
+                   help="--mesh: views that must have seen a voxel before it takes part in a triangle.  The default asks a second view "
+                        "to confirm free or occupied space; a choice, not a measured optimum")
+    p.add_argument("--mesh_budget_gb", type=float, default=16.0,
+                   help="--mesh: GPU memory in GiB that the kept fused views (9 bytes per pixel and view), the volume, the extraction "
+                        "workspace and the mesh buffers may take together; a larger request stops with the bytes it needs.  A choice")
     p.add_argument("--no_pfm", action="store_true",
                    help="--fuse_source memory only: do not write the depth / confidence PFMs, only the PLY (and the masks of "
                         "--save_masks) reaches the disk")
@@ -241,6 +265,18 @@ def check_ply_normals(args) -> bool:
     return True
 
 
+def check_mesh(args) -> bool:
+    """--mesh needs --filter and the GPU point assembly; its numeric flags are checked where the options are built, before any work"""
+    if not _check_gpu_assembly_flag(args, "mesh", "--mesh", "the volume is integrated from the fused depth maps that stay on the GPU"):
+        return False
+    from itermvs_amd import fusion
+    try:
+        fusion.mesh_options_from_args(args, "mesh.ply")
+    except ValueError as e:
+        raise SystemExit("--" + str(e).replace("mesh: ", "mesh_", 1))
+    return True
+
+
 def fuse_memory(args) -> dict:
     """--fuse_source memory: depth maps and point clouds in one pass (itermvs_amd.scan_fuse); scans are sharded over the
     ranks whole, like ``fuse_scans`` shards them.  -> {scan: {ref_view: (geo, photo, final mask share)}} of this rank"""
@@ -248,6 +284,7 @@ def fuse_memory(args) -> dict:
     check_fuse_source(args)
     check_fuse_dedupe(args)
     check_ply_normals(args)
+    check_mesh(args)
     check_feature_cache(args)
     rank, local_rank, world = shard.init_distributed()
     torch.cuda.set_device(local_rank)
@@ -355,6 +392,7 @@ def fuse_scans(args) -> int:
     from itermvs_amd import fusion
     dedupe = check_fuse_dedupe(args)
     normals = check_ply_normals(args)
+    check_mesh(args)
     rank, local_rank, world = shard.init_distributed()
     dev = "cuda:%d" % local_rank
     scans = sorted(d for d in os.listdir(args.testpath)
@@ -367,7 +405,8 @@ def fuse_scans(args) -> int:
                                     args.photo_thres, geo_mask_thres=args.geo_mask_thres, device=dev, img_wh=tuple(args.img_wh),
                                     points=args.fuse_points,
                                     save_masks=args.save_masks, dedupe=dedupe, normals=normals,
-                                    normal_edge_thres=getattr(args, "normal_edge_thres", 0.01))
+                                    normal_edge_thres=getattr(args, "normal_edge_thres", 0.01),
+                                    mesh=fusion.mesh_options_from_args(args, os.path.join(args.outdir, scan + "_mesh.ply")))
         for v, (g, ph, f) in stats.items():
             print("processing {}, ref-view{:0>2}, geo_mask:{:3f} photo_mask:{:3f} final_mask: {:3f}".format(scan, v, g, ph, f))
         n += 1
@@ -380,6 +419,7 @@ if __name__ == "__main__":
     print("argv:", sys.argv[1:])
     check_fuse_dedupe(a)
     check_ply_normals(a)
+    check_mesh(a)
     if check_fuse_source(a) == "memory":
         fuse_memory(a)
     else:

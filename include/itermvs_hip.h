@@ -780,6 +780,65 @@ int itermvs_fuse_points_normals(const double* depth_avg, const uint8_t* final_ma
                                 int64_t* view_counts, int32_t view, uint32_t* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The triangle mesh of a scan (eval.py --mesh; csrc/tsdf.hip, csrc/tsdf_tets.hpp; no counterpart in the reference; numpy
+ * restatement: tests/tsdf_reference.py).  A dense volume of nx * ny * nz voxels, voxel (ix, iy, iz) at index (iz*ny + iy)*nx + ix,
+ * its centre at c = (ox + (ix + 0.5)*voxel, oy + (iy + 0.5)*voxel, oz + (iz + 0.5)*voxel): the index as fp64, + 0.5, * voxel, + the
+ * origin, each rounded once.  All fp64 arithmetic below is without fused multiply-add, sums in the written order, IEEE division.
+ * State: device [n][3] uint32 = 12 bytes per voxel, little-endian: sum_t fp32 | count uint16 | red, green, blue sums uint16.  Running
+ *   sums, not means.  All zero = empty.  A voxel whose count has reached 257 ignores every further view (257 * 255 = 65535 is the
+ *   largest colour sum a uint16 holds), so no field ever wraps.
+ *
+ * itermvs_tsdf_integrate -- folds V >= 1 views of one size into the volume, ONE launch, one thread per voxel; the thread reads its
+ *   state once, walks the views v = 0..V-1 in order and writes the state once.  depth [V][H][W] fp64 and mask [V][H][W] uint8 are
+ *   depth_avg and photo && geo of itermvs_fuse_depth; cams [V][21] fp32 = K (9, row-major) | rows 0..2 of E (12), world -> camera;
+ *   rgb [V][H][W][3] uint8.  Per voxel and view, with K and E upcast to fp64:
+ *   1. count == 257: skip.
+ *   2. pc.x = ((e0*c.x + e1*c.y) + e2*c.z) + e3, pc.y and pc.z with e4..7 and e8..11.  pc.z not finite or <= 0: skip.
+ *   3. u.x = ((k0*pc.x + k1*pc.y) + k2*pc.z) / pc.z, u.y with k3..5 (row 2 of K is taken to be 0 0 1).
+ *   4. px = rint(u.x), py = rint(u.y) (ties to even); unless 0 <= px <= W-1 and 0 <= py <= H-1, compared in fp64 (NaN, inf fail): skip.
+ *   5. mask[v][py][px] == 0: skip.  d = depth[v][py][px] not finite or <= 0: skip.
+ *   6. sdf = d - pc.z; sdf < -trunc: skip (hidden behind the surface).
+ *   7. t = fmin(1, sdf / trunc) in fp64, converted to fp32 once; sum_t += t in fp32; the three colour sums += rgb[v][py][px]; ++count.
+ *   No atomics, nothing depends on scheduling; the same views in batches of any size, in the same order, give the same bits.
+ *   Validation before the launch, in this order: ITERMVS_ERR_NULL for a NULL pointer; ITERMVS_ERR_DIMS for nx, ny or nz < 1, for
+ *   nx*ny*nz beyond the flat bound (2^32 - 256 voxels, csrc/flat_launch.hpp), for voxel not finite or not > 0 or a non-finite origin,
+ *   for trunc not finite or not > 0, for V, H or W < 1 and for H*W > 2^31 - 1.
+ *
+ * itermvs_tsdf_mesh -- marching tetrahedra over the cells; a cell is the cube of the 8 voxel centres (ix..ix+1, iy..iy+1, iz..iz+1)
+ *   and carries the index of its corner 0 (ix, iy, iz); corner bit 0 = +x, bit 1 = +y, bit 2 = +z.
+ *   1. A voxel is valid iff count >= min_count (>= 1); its value is f = sum_t / (float)count in fp32; it is inside iff f < 0 (0 is outside).
+ *   2. A cell is valid iff all 8 corners are valid.  It is cut into the six tetrahedra of the Freudenthal (Kuhn) triangulation,
+ *      tetrahedron 0..5 = the axis orders xyz, xzy, yxz, yzx, zxy, zyx, as cube corners {0,1,3,7} {0,5,1,7} {0,3,2,7} {0,2,6,7} {0,4,5,7}
+ *      {0,6,4,7} (all positively oriented), and each tetrahedron emits the 0, 1 or 2 triangles of its 4-bit inside mask by the rule in
+ *      csrc/tsdf_tets.hpp (itermvs_tsdf_tet_corners and itermvs_tsdf_tet_case fill in both tables; the latter returns the number of triangles).  Triangles are counter-clockwise seen
+ *      from the positive side.
+ *   3. A vertex exists for (voxel a, direction) iff a valid cell has that edge and its two ends differ in inside.  Directions
+ *      0..6 = +x, +y, +z, +xy, +xz, +yz, +xyz lead to the neighbour b.  With fa, fb the fp32 values: s = (double)fa / ((double)fa -
+ *      (double)fb); each coordinate is ca + s * (cb - ca) from the two centres' coordinates, converted to fp32 once; each colour
+ *      channel is qa + s * (qb - qa) with q = (double)sum / (double)count, then rint, clamped to 0..255, converted to uint8.
+ *   4. Vertices are numbered in ascending (voxel index, direction); triangles in ascending (cell index, tetrahedron, triangle of the case).
+ *   vertices: `vertex_capacity` records of 15 bytes, unpadded (x, y, z little-endian float32; red, green, blue uint8); faces:
+ *   `face_capacity` triples of int32 vertex indices.  A vertex or triangle whose number is >= its capacity is not stored; totals
+ *   (device uint64 [2] = vertices, triangles) holds the true totals all the same, so the caller sees the overflow.  The stored
+ *   triangles always hold the true vertex numbers.  Nothing outside vertices[0 : 15*vertex_capacity], faces[0 : 3*face_capacity],
+ *   totals and the workspace is written.  One memset and five launches (mark, count, one-workgroup scan, vertex, face); the marks
+ *   are plain byte stores of the constant 1; no atomics, no workgroup waits on another.
+ *   workspace: the *bytes of itermvs_tsdf_mesh_workspace_bytes(nx, ny, nz, bytes) (16 per 256 voxels + 12 per voxel), 8-byte aligned.
+ *   Validation before any HIP call: ITERMVS_ERR_NULL for NULL state, totals, workspace, or NULL vertices / faces with a capacity
+ *   other than 0; ITERMVS_ERR_DIMS as for the volume above, for min_count < 1, a capacity < 0 and vertex_capacity > 2^31 - 1;
+ *   ITERMVS_ERR_ALIGN for the workspace.
+ * ------------------------------------------------------------------------------------------ */
+int itermvs_tsdf_tet_corners(int32_t tet, int32_t* corners /* host [4] */);
+int itermvs_tsdf_tet_case(int32_t mask, int32_t* edges /* host [12]: triangle t, vertex v = local corners [6t+2v], [6t+2v+1]; -1 beyond */);
+int itermvs_tsdf_integrate(uint32_t* state, int32_t nx, int32_t ny, int32_t nz, double ox, double oy, double oz, double voxel,
+                           double trunc, const double* depth, const uint8_t* mask, const float* cams, const uint8_t* rgb,
+                           int32_t V, int32_t H, int32_t W, void* stream);
+int itermvs_tsdf_mesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz, int64_t* bytes /* host */);
+int itermvs_tsdf_mesh(const uint32_t* state, int32_t nx, int32_t ny, int32_t nz, double ox, double oy, double oz, double voxel,
+                      int32_t min_count, uint8_t* vertices, int64_t vertex_capacity, int32_t* faces, int64_t face_capacity,
+                      uint64_t* totals, uint8_t* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The COLMAP converter's two device stages (csrc/colmap.hip; colmap_input.py of the reference, host side: itermvs_amd/colmap.py).
  * Common inputs (device): the images' observation lists as CSR -- offsets [V+1] int64 ascending, point [offsets[V]] int32 = dense
  *   point index into xyz or -1, in file order (image index = position in images.bin) -- and xyz [P][3] fp64.  An entry outside

@@ -208,6 +208,13 @@ PROTOTYPES = {
                                       C.c_int32, C.c_void_p, C.c_void_p]),
     "itermvs_fuse_points_normals": (C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
                                               C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "itermvs_tsdf_tet_corners": (C.c_int, [C.c_int32, C.POINTER(C.c_int32)]),
+    "itermvs_tsdf_tet_case": (C.c_int, [C.c_int32, C.POINTER(C.c_int32)]),
+    "itermvs_tsdf_integrate": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.c_double] * 5 + [C.c_void_p] * 4 + [C.c_int32] * 3 +
+                                         [C.c_void_p]),
+    "itermvs_tsdf_mesh_workspace_bytes": (C.c_int, [C.c_int32] * 3 + [C.POINTER(C.c_int64)]),
+    "itermvs_tsdf_mesh": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.c_double] * 4 + [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                    C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "itermvs_view_scores": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p,
                                       C.c_void_p]),
     "itermvs_depth_ranges": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

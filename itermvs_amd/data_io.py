@@ -110,3 +110,65 @@ def read_ply_xyz(filename: str) -> np.ndarray:
         if data.shape[0] != n:
             raise bad(f"{data.shape[0]} of {n} vertices: the file is short")
     return np.stack([data["x"].astype(np.float32), data["y"].astype(np.float32), data["z"].astype(np.float32)], 1)
+
+
+def read_ply_mesh(filename: str):
+    """a binary little-endian triangle mesh as ``fusion.write_ply_mesh`` writes it (``eval.py --mesh``) -> (xyz float32 [N,3], rgb
+    uint8 [N,3] or None when the vertices carry no colour, faces int32 [M,3]).  The vertex element comes first and holds scalar
+    properties with x, y, z; the face element follows with ONE property, ``list uchar int vertex_indices`` (``uint`` and the
+    name ``vertex_index`` are accepted).  Anything else -- ascii, a face that is no triangle, an index outside the vertices, a short
+    or overlong file -- raises a ValueError naming the file."""
+    def bad(why: str) -> ValueError:
+        return ValueError(f"{filename}: {why}")
+
+    with open(filename, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise bad("not a PLY file")
+        fmt, elements, props, face_props, current = None, [], [], [], None
+        while True:
+            raw = f.readline()
+            if not raw:
+                raise bad("PLY header without end_header")
+            words = raw.decode("ascii", "replace").split()
+            if not words or words[0] in ("comment", "obj_info"):
+                continue
+            if words[0] == "end_header":
+                break
+            if words[0] == "format" and len(words) >= 2:
+                fmt = words[1]
+            elif words[0] == "element" and len(words) == 3:
+                current = words[1]
+                elements.append((current, int(words[2])))
+            elif words[0] == "property" and current == "vertex":
+                if len(words) != 3 or words[1] not in _PLY_TYPES:
+                    raise bad(f"unsupported vertex property {' '.join(words[1:])!r}")
+                props.append((words[2], _PLY_TYPES[words[1]]))
+            elif words[0] == "property" and current == "face":
+                face_props.append(words[1:])
+        if fmt != "binary_little_endian":
+            raise bad(f"format {fmt!r} is not supported (binary_little_endian is)")
+        if [e[0] for e in elements] != ["vertex", "face"]:
+            raise bad(f"expected the elements vertex, face, got {[e[0] for e in elements]}")
+        names = [p[0] for p in props]
+        if len(set(names)) != len(names) or any(a not in names for a in "xyz"):
+            raise bad(f"the vertex element needs x, y and z once each, has {names}")
+        if len(face_props) != 1 or face_props[0][:2] != ["list", "uchar"] or len(face_props[0]) != 4 or \
+                face_props[0][2] not in ("int", "int32", "uint", "uint32") or face_props[0][3] not in ("vertex_indices", "vertex_index"):
+            raise bad(f"the face element needs one property list uchar int vertex_indices, has {face_props}")
+        (_, n), (_, m) = elements
+        data = np.fromfile(f, dtype=np.dtype([(name, "<" + t) for name, t in props]), count=n)
+        if data.shape[0] != n:
+            raise bad(f"{data.shape[0]} of {n} vertices: the file is short")
+        rows = np.fromfile(f, dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]), count=m)
+        if rows.shape[0] != m:
+            raise bad(f"{rows.shape[0]} of {m} faces: the file is short")
+        if f.read(1):
+            raise bad("bytes after the last face")
+    if m and (rows["n"] != 3).any():
+        raise bad("a face that is not a triangle")
+    faces = np.ascontiguousarray(rows["v"])
+    if m and (faces.min() < 0 or faces.max() >= n):
+        raise bad(f"a vertex index outside 0..{n - 1}")
+    xyz = np.stack([data[a].astype(np.float32) for a in "xyz"], 1)
+    rgb = np.stack([data[a].astype(np.uint8) for a in ("red", "green", "blue")], 1) if all(a in names for a in ("red", "green", "blue")) else None
+    return xyz, rgb, faces

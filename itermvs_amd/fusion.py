@@ -6,9 +6,11 @@ layout of eval.py:298-308 (x, y, z float32; red, green, blue uint8)."""
 from __future__ import annotations
 
 import contextlib
+import dataclasses
+import math
 import os
 import time
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -161,11 +163,177 @@ def _download(records: torch.Tensor, nbytes: int, write, seconds: Dict[str, floa
     return n_chunks
 
 
+MESH_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+MESH_FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])            # property list uchar int vertex_indices: 13 bytes
+MESH_KEPT_BYTES_PER_PIXEL = 9                                      # depth_avg float64 + (photo & geo) uint8 per reference view
+MESH_INTEGRATE_BATCH = 4                                           # views per itermvs_tsdf_integrate launch (profiles/mesh/README.md)
+
+
+@dataclasses.dataclass
+class MeshOptions:
+    """what ``fuse_scan(mesh=...)`` needs.  path: the mesh PLY.  bounds: (x0, y0, z0, x1, y1, z1) of the volume, used as given; None:
+    the ``bounds_quantile`` rule of ``mesh_bounds`` on the emitted cloud, widened by the truncation distance.  voxel: the voxel's
+    side; None: the longest side of the (unwidened) bounds / ``resolution``.  trunc_voxels: truncation distance in voxels.
+    min_count: views a voxel needs to be valid.  budget_bytes: GPU memory the kept views, the volume, the extraction workspace and
+    the mesh buffers may take together.  batch_views: views per integrate launch.  The defaults are choices, not measured optima."""
+    path: str
+    bounds: Optional[Sequence[float]] = None
+    bounds_quantile: float = 0.01
+    voxel: Optional[float] = None
+    resolution: int = 256
+    trunc_voxels: float = 3.0
+    min_count: int = 2
+    budget_bytes: int = 16 << 30
+    batch_views: int = MESH_INTEGRATE_BATCH
+
+
+def mesh_options(mesh) -> Optional[MeshOptions]:
+    """None, a ``MeshOptions`` or a dict of its fields -> a checked ``MeshOptions`` or None"""
+    if mesh is None:
+        return None
+    m = mesh if isinstance(mesh, MeshOptions) else MeshOptions(**dict(mesh))
+    finite = lambda x: -float("inf") < float(x) < float("inf")           # noqa: E731
+    if m.bounds is not None:
+        b = tuple(float(x) for x in m.bounds)
+        if len(b) != 6 or not all(finite(x) for x in b) or not all(b[i] < b[i + 3] for i in range(3)):
+            raise ValueError(f"mesh: bounds must be six finite numbers x0 y0 z0 x1 y1 z1 with x0 < x1, y0 < y1, z0 < z1, got {m.bounds}")
+        m = dataclasses.replace(m, bounds=b)
+    if not 0 <= m.bounds_quantile < 0.5:
+        raise ValueError(f"mesh: bounds_quantile must be in [0, 0.5), got {m.bounds_quantile}")
+    if m.voxel is not None and not (finite(m.voxel) and m.voxel > 0):
+        raise ValueError(f"mesh: voxel must be finite and above 0, got {m.voxel}")
+    if int(m.resolution) < 2:
+        raise ValueError(f"mesh: resolution must be at least 2 voxels, got {m.resolution}")
+    if not (finite(m.trunc_voxels) and m.trunc_voxels >= 1):
+        raise ValueError(f"mesh: trunc_voxels must be finite and at least 1 (a thinner band misses the voxels next to the surface), "
+                         f"got {m.trunc_voxels}")
+    if int(m.min_count) < 1 or int(m.batch_views) < 1 or int(m.budget_bytes) < 1:
+        raise ValueError(f"mesh: min_count, batch_views and budget_bytes must be at least 1, got {m.min_count}, {m.batch_views}, "
+                         f"{m.budget_bytes}")
+    return m
+
+
+def mesh_options_from_args(args, path: str) -> Optional[MeshOptions]:
+    """the ``--mesh*`` flags of eval.py -> ``MeshOptions`` writing ``path``, or None without ``--mesh``"""
+    if not getattr(args, "mesh", False):
+        return None
+    return mesh_options(MeshOptions(path=path, bounds=getattr(args, "mesh_bounds", None),
+                                    bounds_quantile=getattr(args, "mesh_bounds_quantile", 0.01), voxel=getattr(args, "mesh_voxel", None),
+                                    resolution=getattr(args, "mesh_resolution", 256), trunc_voxels=getattr(args, "mesh_trunc", 3.0),
+                                    min_count=getattr(args, "mesh_min_count", 2),
+                                    budget_bytes=int(getattr(args, "mesh_budget_gb", 16.0) * (1 << 30))))
+
+
+def mesh_bounds(xyz, quantile: float) -> Tuple[float, ...]:
+    """the default volume of a cloud, before widening: per axis the ``quantile`` and ``1 - quantile`` order statistics of the
+    finite vertices' coordinates, exact by sort and without interpolation: sorted[k] and sorted[n - 1 - k], k = floor(quantile *
+    (n - 1)).  xyz: [n,3] torch tensor (either device) or array.  -> (x0, y0, z0, x1, y1, z1)"""
+    t = (xyz if torch.is_tensor(xyz) else torch.from_numpy(np.ascontiguousarray(xyz))).reshape(-1, 3)
+    t = t[torch.isfinite(t).all(dim=1)]
+    n = t.shape[0]
+    if n == 0:
+        raise ValueError("mesh_bounds: no finite vertex")
+    k = int(math.floor(float(quantile) * (n - 1)))
+    s = torch.sort(t, dim=0).values
+    lo, hi = s[k].tolist(), s[n - 1 - k].tolist()
+    return tuple(float(v) for v in (*lo, *hi))
+
+
+def mesh_plan(bounds: Sequence[float], voxel: Optional[float] = None, resolution: int = 256, trunc_voxels: float = 3.0,
+              widen: bool = True, budget_bytes: int = None, other_bytes: int = 0) -> dict:
+    """the volume of a mesh: voxel = ``voxel`` or the longest side of ``bounds`` / ``resolution``; trunc = trunc_voxels * voxel;
+    ``widen``: the bounds grow by trunc on every side; dims = ceil(side / voxel) per axis (at least 2, a cell needs two voxels).
+    -> {origin, voxel, trunc, dims, state_bytes, workspace_bytes}.  Raises before anything is allocated when state + workspace +
+    ``other_bytes`` (what the caller already holds for the mesh) exceed ``budget_bytes``, or the voxel count the 2^32 - 256 of one launch."""
+    b = [float(x) for x in bounds]
+    sides = [b[i + 3] - b[i] for i in range(3)]
+    if not all(s > 0 and s < float("inf") for s in sides):
+        raise ValueError(f"mesh_plan: bounds without extent: {tuple(b)}")
+    vox = float(voxel) if voxel is not None else max(sides) / int(resolution)
+    trunc = float(trunc_voxels) * vox
+    origin = [b[i] - (trunc if widen else 0.0) for i in range(3)]
+    dims = [max(2, int(math.ceil((sides[i] + (2 * trunc if widen else 0.0)) / vox))) for i in range(3)]
+    n = dims[0] * dims[1] * dims[2]
+    state_bytes = n * ops.TSDF_VOXEL_BYTES
+    workspace_bytes = 16 * ((n + 255) // 256) + 12 * n               # itermvs_tsdf_mesh_workspace_bytes, without the library
+    need = state_bytes + workspace_bytes + int(other_bytes)
+    hint = "lower --mesh_resolution, raise --mesh_voxel or tighten --mesh_bounds"
+    if n > (1 << 32) - 256:
+        raise ValueError(f"mesh: a volume of {dims[0]}x{dims[1]}x{dims[2]} voxels is beyond the {(1 << 32) - 256} of one launch; {hint}")
+    if budget_bytes is not None and need > budget_bytes:
+        raise ValueError(f"mesh: a volume of {dims[0]}x{dims[1]}x{dims[2]} voxels needs {need} bytes on the GPU ({state_bytes} state, "
+                         f"{workspace_bytes} extraction workspace, {int(other_bytes)} kept views), the budget is {budget_bytes}; "
+                         f"{hint}, or raise --mesh_budget_gb")
+    return dict(origin=tuple(origin), voxel=vox, trunc=trunc, dims=tuple(dims), state_bytes=state_bytes,
+                workspace_bytes=workspace_bytes, need_bytes=need)
+
+
+def ply_mesh_header(n_vertices: int, n_faces: int) -> bytes:
+    return ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+            "property uchar red\nproperty uchar green\nproperty uchar blue\nelement face %d\n"
+            "property list uchar int vertex_indices\nend_header\n" % (n_vertices, n_faces)).encode("ascii")
+
+
+def write_ply_mesh(filename: str, vertices: np.ndarray, faces: np.ndarray) -> None:
+    """binary little-endian PLY: ``vertices`` MESH_VERTEX [n] (or their uint8 bytes), ``faces`` int32 [m,3]"""
+    vertices = np.ascontiguousarray(vertices).view(np.uint8).reshape(-1, MESH_VERTEX.itemsize)
+    faces = np.asarray(faces, np.int32).reshape(-1, 3)
+    rows = np.empty(len(faces), MESH_FACE)
+    rows["n"], rows["v"] = 3, faces
+    with _remove_on_error(filename), open(filename, "wb") as f:
+        f.write(ply_mesh_header(len(vertices), len(faces)))
+        f.write(vertices.tobytes())
+        f.write(rows.tobytes())
+
+
+def extract_mesh(state: torch.Tensor, plan: dict, min_count: int, budget_bytes: int = None, used_bytes: int = 0):
+    """marching tetrahedra over an integrated volume -> (vertex bytes uint8 [nv*15], faces int32 [nf*3]) on the GPU.  Two runs of
+    ``itermvs_tsdf_mesh``: the first with capacities 0 for the totals, the second into buffers of exactly that size; between them the
+    buffers are checked against what the budget has left."""
+    dev = state.device
+    args = (state, plan["dims"], plan["origin"], plan["voxel"], int(min_count))
+    totals = torch.zeros(2, device=dev, dtype=torch.int64)
+    workspace = torch.empty(ops.tsdf_mesh_workspace_bytes(plan["dims"]), device=dev, dtype=torch.uint8)
+    ops.tsdf_mesh(*args, torch.empty(0, device=dev, dtype=torch.uint8), torch.empty(0, device=dev, dtype=torch.int32), totals, workspace)
+    nv, nf = (int(t) for t in totals.tolist())
+    out_bytes = nv * ops.MESH_VERTEX_BYTES + nf * ops.MESH_FACE_BYTES
+    if nv > 0x7fffffff:
+        raise ValueError(f"mesh: {nv} vertices do not fit the int32 indices of a PLY face; lower --mesh_resolution or raise --mesh_voxel")
+    if budget_bytes is not None and used_bytes + out_bytes > budget_bytes:
+        raise ValueError(f"mesh: {nv} vertices and {nf} triangles need {out_bytes} bytes on top of {used_bytes}, the budget is "
+                         f"{budget_bytes}; lower --mesh_resolution, raise --mesh_voxel or raise --mesh_budget_gb")
+    vertices = torch.empty(nv * ops.MESH_VERTEX_BYTES, device=dev, dtype=torch.uint8)
+    faces = torch.empty(nf * 3, device=dev, dtype=torch.int32)
+    if nv or nf:
+        ops.tsdf_mesh(*args, vertices, faces, totals, workspace)
+    return vertices, faces
+
+
+def write_scan_mesh(mesh: MeshOptions, bounds: Sequence[float], depth: torch.Tensor, mask: torch.Tensor, cams: torch.Tensor,
+                    rgb: torch.Tensor, info: dict = None) -> None:
+    """the kept views (depth float64 [V,H,W], mask uint8 [V,H,W], cams float32 [V,21] = K | E[:3], rgb uint8 [V,H,W,3], on the GPU, in
+    pair.txt order) -> ``mesh.path``: the volume of ``mesh_plan``, ``itermvs_tsdf_integrate`` in batches of ``mesh.batch_views``,
+    ``extract_mesh``, one download"""
+    v, h, w = depth.shape
+    kept = v * h * w * MESH_KEPT_BYTES_PER_PIXEL
+    plan = mesh_plan(bounds, mesh.voxel, mesh.resolution, mesh.trunc_voxels, widen=mesh.bounds is None,
+                     budget_bytes=mesh.budget_bytes, other_bytes=kept)
+    state = ops.tsdf_volume(plan["dims"], depth.device)
+    for a in range(0, v, int(mesh.batch_views)):
+        b = min(a + int(mesh.batch_views), v)
+        ops.tsdf_integrate(state, plan["dims"], plan["origin"], plan["voxel"], plan["trunc"], depth[a:b], mask[a:b], cams[a:b], rgb[a:b])
+    vertices, faces = extract_mesh(state, plan, mesh.min_count, mesh.budget_bytes, plan["need_bytes"])
+    write_ply_mesh(mesh.path, vertices.cpu().numpy(), faces.cpu().numpy())
+    if info is not None:
+        info.update(plan, bounds=tuple(bounds), vertices=vertices.numel() // ops.MESH_VERTEX_BYTES, faces=faces.numel() // 3,
+                    batches=(v + int(mesh.batch_views) - 1) // int(mesh.batch_views))
+
+
 def fuse_scan(pairs: Sequence[Tuple[int, Sequence[int]]], cams, depths, confidences, images, plyfilename: str,
               geo_pixel_thres: float, geo_depth_thres: float, photo_thres: float, geo_mask_thres: int = 3, device: str = "cuda",
               records_budget: int = 2 << 30, mask_folder: str = None, group_capacity: int = None,
               info: dict = None, dedupe: bool = False, normals: bool = False,
-              normal_edge_thres: float = 0.01) -> Dict[int, Tuple[float, float, float]]:
+              normal_edge_thres: float = 0.01, mesh=None) -> Dict[int, Tuple[float, float, float]]:
     """eval.py:215-309 for a scan that is already in memory, with the point cloud assembled on the GPU: per reference view one
     ``itermvs_fuse_depth`` and one ``itermvs_fuse_points``, enqueued back to back; the host synchronises once per GROUP of
     reference views, downloads the group's finished vertex records and appends them to the PLY.
@@ -184,8 +352,14 @@ def fuse_scan(pairs: Sequence[Tuple[int, Sequence[int]]], cams, depths, confiden
     the header of ``ply_header(n, normals=True)``): the unit normal of the averaged depth map's surface at the pixel, facing the
     reference camera; ``normal_edge_thres``: relative depth step beyond which a neighbouring pixel is not used for it.  The
     vertices, their order and every other byte are those without it.
+    mesh: ``MeshOptions`` (or a dict of its fields; None: off) -- also write a triangle mesh of the scan (``write_scan_mesh``): every
+    reference view's ``depth_avg`` and ``photo & geo`` stay on the GPU while the cloud is assembled (9 bytes per pixel and view, part
+    of the mesh's budget), the emitted vertices' coordinates are kept for the default bounds, and after the last group the views are
+    integrated into a volume in ``pairs`` order and marching tetrahedra writes ``mesh.path``.  The cloud, the masks and the
+    returned shares are those without it.
     -> {ref_view: (geo, photo, final mask share)} like ``filter_depth``."""
     dev = torch.device(device)
+    mesh = mesh_options(mesh)
     clock = time.perf_counter
     seconds = {"upload": 0.0, "enqueue": 0.0, "gpu_wait": 0.0, "download_wait": 0.0, "file_write": 0.0, "mask_write": 0.0}
     n_sync = n_chunks = 0
@@ -216,6 +390,16 @@ def fuse_scan(pairs: Sequence[Tuple[int, Sequence[int]]], cams, depths, confiden
         first_mat = np.cumsum([0] + [len(m) for m in mats])
         mats = torch.from_numpy(np.concatenate(mats)).to(dev) if pairs else None
         cam = torch.from_numpy(np.stack(cam).astype(np.float32)).to(dev) if pairs else None
+        if mesh is not None and pairs:
+            kept_bytes = len(pairs) * h * w * MESH_KEPT_BYTES_PER_PIXEL
+            if kept_bytes > mesh.budget_bytes:
+                raise ValueError(f"mesh: keeping {len(pairs)} fused {w}x{h} views on the GPU takes {kept_bytes} bytes, the budget is "
+                                 f"{mesh.budget_bytes} (mesh budget_bytes)")
+            keep_depth = torch.empty((len(pairs), h, w), device=dev, dtype=torch.float64)
+            keep_mask = torch.empty((len(pairs), h, w), device=dev, dtype=torch.uint8)
+            rgb_all = torch.stack(rgb)
+            rgb = list(rgb_all)                                        # the views the emit kernels read, now of one tensor
+            cloud_xyz = []
         groups = group_views(len(pairs), h, w, records_budget, rec)
         capacity = max((b - a) * h * w for a, b in groups) if group_capacity is None and groups else int(group_capacity or 0)
         records = torch.empty(capacity * rec, device=dev, dtype=torch.uint8)
@@ -243,6 +427,9 @@ def fuse_scan(pairs: Sequence[Tuple[int, Sequence[int]]], cams, depths, confiden
                     emit(avg, final, cam[i], rgb[i], records, cursor, counts, i, photo, geo, capacity, workspace, **emit_options)
                     if mask_folder is not None:
                         masks.append((ref, photo, geo, final))
+                    if mesh is not None:
+                        keep_depth[i].copy_(avg)
+                        keep_mask[i].copy_((photo != 0) & (geo != 0))
                 host[a:b].copy_(counts[a:b], non_blocking=True)
                 host[-1, :1].copy_(cursor, non_blocking=True)
                 t1 = clock()
@@ -259,6 +446,8 @@ def fuse_scan(pairs: Sequence[Tuple[int, Sequence[int]]], cams, depths, confiden
                     ph, g, fin = (int(c) / float(h * w) for c in host[i, :3])
                     stats[pairs[i][0]] = (g, ph, fin)
                 n_vertices += n
+                if mesh is not None and mesh.bounds is None and n:
+                    cloud_xyz.append(records[:n * rec].view(n, rec)[:, :12].contiguous().view(torch.float32))
                 if b == len(pairs):                                    # the total is known: header, earlier groups, then stream
                     t3 = clock()
                     f.write(ply_header(n_vertices, normals))
@@ -274,7 +463,23 @@ def fuse_scan(pairs: Sequence[Tuple[int, Sequence[int]]], cams, depths, confiden
                 seconds["mask_write"] += clock() - t3
             if not groups:
                 f.write(ply_header(0, normals))
+        if mesh is not None:
+            mesh_info = {}
+            if pairs:
+                bounds = mesh.bounds
+                if bounds is None:
+                    if not cloud_xyz:
+                        raise ValueError("mesh: the cloud is empty, there is nothing to take the default bounds from (give bounds)")
+                    bounds = mesh_bounds(torch.cat(cloud_xyz), mesh.bounds_quantile)
+                del cloud_xyz
+                kcam = np.stack([np.concatenate([f32(cams[ref][0]).reshape(-1), f32(cams[ref][1])[:3].reshape(-1)])
+                                 for ref, _ in pairs]).astype(np.float32)
+                write_scan_mesh(mesh, bounds, keep_depth, keep_mask, torch.from_numpy(kcam).to(dev), rgb_all, info=mesh_info)
+            else:
+                write_ply_mesh(mesh.path, np.zeros(0, MESH_VERTEX), np.zeros((0, 3), np.int32))
     if info is not None:
+        if mesh is not None:
+            info.update(mesh=mesh_info)
         info.update(groups=groups, synchronisations=n_sync, downloads=len(groups), download_chunks=n_chunks,
                     vertices=n_vertices, capacity=capacity, seconds=seconds, dedupe=bool(dedupe),
                     normals=bool(normals), record_bytes=rec)
@@ -285,7 +490,7 @@ def filter_depth(scan_folder: str, out_folder: str, plyfilename: str, geo_pixel_
                  photo_thres: float, images: Dict[int, np.ndarray] = None, intrinsics_scale: Tuple[float, float] = None,
                  geo_mask_thres: int = 3, device: str = "cuda", img_wh: Tuple[int, int] = None, points: str = "host",
                  save_masks: bool = False, records_budget: int = 2 << 30, info: dict = None,
-                 dedupe: bool = False, normals: bool = False, normal_edge_thres: float = 0.01) -> Dict[str, float]:
+                 dedupe: bool = False, normals: bool = False, normal_edge_thres: float = 0.01, mesh=None) -> Dict[str, float]:
     """eval.py:215-309: for every reference view of ``pair.txt`` fuse its depth map with its source views' and append the
     surviving pixels to one point cloud.
 
@@ -302,7 +507,7 @@ def filter_depth(scan_folder: str, out_folder: str, plyfilename: str, geo_pixel_
     ``fuse_scan``); same header, vertex order and colours, coordinates equal up to the last float64 bit of ``np.matmul``.
     ``save_masks``: also write ``<out_folder>/mask/{view:0>8}_photo.png``, ``_geo.png``, ``_final.png`` (eval.py:266-269).
     ``dedupe``: ``fuse_scan``'s, so it needs ``points="device"``.  ``normals``, ``normal_edge_thres``: ``fuse_scan``'s, with the
-    same need."""
+    same need; ``mesh``: ``fuse_scan``'s, with the same need."""
     if points not in ("host", "device"):
         raise ValueError(f"filter_depth: points must be 'host' or 'device', got {points!r}")
     if dedupe and points != "device":
@@ -311,6 +516,9 @@ def filter_depth(scan_folder: str, out_folder: str, plyfilename: str, geo_pixel_
     if normals and points != "device":
         raise ValueError("filter_depth: normals=True needs points='device' (the normals are computed from the fused depth map on "
                          f"the GPU while the vertices are emitted), got points={points!r}")
+    if mesh is not None and points != "device":
+        raise ValueError("filter_depth: mesh needs points='device' (the volume is integrated from the fused depth maps that stay on "
+                         f"the GPU), got points={points!r}")
     pairs = read_pair_file(os.path.join(scan_folder, "pair.txt"))
     mask_folder = os.path.join(out_folder, "mask") if save_masks else None
     if img_wh is None and images is None and intrinsics_scale is None:
@@ -367,7 +575,7 @@ def filter_depth(scan_folder: str, out_folder: str, plyfilename: str, geo_pixel_
                 rgb[ref_view] = pixels.pop(ref_view) if ref_view in pixels else np.full((h, w, 3), 127, np.uint8)
         return fuse_scan(pairs, cams, depths, confs, rgb, plyfilename, geo_pixel_thres, geo_depth_thres, photo_thres,
                          geo_mask_thres, device, records_budget, mask_folder, info=info, dedupe=dedupe, normals=normals,
-                         normal_edge_thres=normal_edge_thres)
+                         normal_edge_thres=normal_edge_thres, mesh=mesh)
 
     vertexs, colors, stats = [], [], {}
     for ref_view, src_views in pairs:

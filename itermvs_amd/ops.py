@@ -1426,6 +1426,95 @@ def fuse_points_normals(depth_avg: Tensor, final_mask: Tensor, cam: Tensor, rgb:
                  view, photo_mask, geo_mask, capacity, workspace, extra=(float(edge_thres),))
 
 
+TSDF_VOXEL_BYTES = 12        # sum_t float32 | count uint16 | red, green, blue sums uint16 (include/itermvs_hip.h)
+MESH_VERTEX_BYTES = 15       # x, y, z float32, red, green, blue uint8
+MESH_FACE_BYTES = 12         # three int32 vertex indices
+
+
+def _tsdf_tensor(what: str, name: str, t, dtype, shape=None) -> None:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{what}: {name}: expected a CUDA/ROCm tensor - the IterMVS HIP engine has no CPU path")
+    if t.dtype != dtype or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise RuntimeError(f"{what}: {name} must be a contiguous {dtype} tensor" + (f" of shape {tuple(shape)}" if shape else "") +
+                           f", got {t.dtype} {tuple(t.shape)}")
+
+
+def tsdf_tet_tables() -> Tuple[List[List[int]], List[List[List[Tuple[int, int]]]]]:
+    """the two tables of csrc/tsdf_tets.hpp through the library's host functions (no GPU): (corners [6][4] as cube corners,
+    cases [16] = list of triangles, each three edges (lower, upper local corner))"""
+    lib = _lib.load()
+    buf4, buf12 = (C.c_int32 * 4)(), (C.c_int32 * 12)()
+    corners, cases = [], []
+    for t in range(6):
+        check(lib.itermvs_tsdf_tet_corners(t, buf4), "itermvs_tsdf_tet_corners")
+        corners.append(list(buf4))
+    for m in range(16):
+        n = lib.itermvs_tsdf_tet_case(m, buf12)
+        check(min(n, 0), "itermvs_tsdf_tet_case")
+        cases.append([[(buf12[6 * t + 2 * v], buf12[6 * t + 2 * v + 1]) for v in range(3)] for t in range(n)])
+    return corners, cases
+
+
+def tsdf_volume(dims: Sequence[int], device) -> Tensor:
+    """an empty volume state for ``tsdf_integrate``: int32 [nx*ny*nz, 3], all zero"""
+    nx, ny, nz = (int(d) for d in dims)
+    return torch.zeros((nx * ny * nz, 3), device=device, dtype=torch.int32)
+
+
+def tsdf_integrate(state: Tensor, dims: Sequence[int], origin: Sequence[float], voxel: float, trunc: float, depth: Tensor,
+                   mask: Tensor, cams: Tensor, rgb: Tensor) -> None:
+    """itermvs_tsdf_integrate: folds the V views depth float64 [V,H,W] (``depth_avg``), mask uint8 [V,H,W] (photo & geo), cams
+    float32 [V,21] = K | E[:3] (world -> camera), rgb uint8 [V,H,W,3] into ``state`` (int32 [nx*ny*nz,3], ``tsdf_volume``) IN PLACE,
+    in the given order, one launch; nothing is read back.  The contract is in include/itermvs_hip.h."""
+    nx, ny, nz = (int(d) for d in dims)
+    what = "tsdf_integrate"
+    _tsdf_tensor(what, "depth", depth, torch.float64)
+    if depth.dim() != 3:
+        raise RuntimeError(f"{what}: depth must be [V,H,W], got {tuple(depth.shape)}")
+    v, h, w = depth.shape
+    _tsdf_tensor(what, "state", state, torch.int32, (nx * ny * nz, 3))
+    _tsdf_tensor(what, "mask", mask, torch.uint8, (v, h, w))
+    _tsdf_tensor(what, "cams", cams, torch.float32, (v, 21))
+    _tsdf_tensor(what, "rgb", rgb, torch.uint8, (v, h, w, 3))
+    check(_lib.load().itermvs_tsdf_integrate(state.data_ptr(), nx, ny, nz, *(float(o) for o in origin), float(voxel), float(trunc),
+                                             depth.data_ptr(), mask.data_ptr(), cams.data_ptr(), rgb.data_ptr(), v, h, w, _stream()),
+          "itermvs_tsdf_integrate")
+
+
+def tsdf_mesh_workspace_bytes(dims: Sequence[int]) -> int:
+    n = C.c_int64(0)
+    check(_lib.load().itermvs_tsdf_mesh_workspace_bytes(*(int(d) for d in dims), C.byref(n)), "itermvs_tsdf_mesh_workspace_bytes")
+    return int(n.value)
+
+
+def tsdf_mesh(state: Tensor, dims: Sequence[int], origin: Sequence[float], voxel: float, min_count: int, vertices: Tensor,
+              faces: Tensor, totals: Tensor, workspace: Optional[Tensor] = None, vertex_capacity: Optional[int] = None,
+              face_capacity: Optional[int] = None) -> None:
+    """itermvs_tsdf_mesh: marching tetrahedra over ``state`` -> ``vertices`` (uint8, 15 bytes each), ``faces`` (int32 [F,3] or flat)
+    and ``totals`` (int64 [2]: vertices, triangles that exist, whatever the capacities); nothing is read back.  The capacities
+    default to all of the two buffers; ``workspace``: uint8 scratch of tsdf_mesh_workspace_bytes(dims), allocated here when not given."""
+    nx, ny, nz = (int(d) for d in dims)
+    what = "tsdf_mesh"
+    _tsdf_tensor(what, "state", state, torch.int32, (nx * ny * nz, 3))
+    _tsdf_tensor(what, "vertices", vertices, torch.uint8)
+    _tsdf_tensor(what, "faces", faces, torch.int32)
+    _tsdf_tensor(what, "totals", totals, torch.int64, (2,))
+    vcap = vertices.numel() // MESH_VERTEX_BYTES if vertex_capacity is None else int(vertex_capacity)
+    fcap = faces.numel() // 3 if face_capacity is None else int(face_capacity)
+    if vcap < 0 or vcap * MESH_VERTEX_BYTES > vertices.numel() or fcap < 0 or fcap * 3 > faces.numel():
+        raise RuntimeError(f"{what}: capacities {vcap} vertices, {fcap} triangles do not fit the buffers "
+                           f"({vertices.numel()} bytes, {faces.numel()} indices)")
+    need = tsdf_mesh_workspace_bytes(dims)
+    if workspace is None:
+        workspace = torch.empty(need, device=state.device, dtype=torch.uint8)
+    elif not workspace.is_cuda or workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous():
+        raise RuntimeError(f"{what}: workspace must be a contiguous uint8 CUDA/ROCm tensor of >= {need} bytes")
+    check(_lib.load().itermvs_tsdf_mesh(state.data_ptr(), nx, ny, nz, *(float(o) for o in origin), float(voxel), int(min_count),
+                                        vertices.data_ptr() if vcap else None, vcap, faces.data_ptr() if fcap else None, fcap,
+                                        totals.data_ptr(), workspace.data_ptr(), _stream()),
+          "itermvs_tsdf_mesh")
+
+
 def _colmap_inputs(what: str, offsets: Tensor, point: Tensor, xyz: Tensor, per_view: Tensor, width: int) -> Tuple[int, int]:
     """shared checks of view_scores / depth_ranges -> (V, P).  ``offsets`` is the one HOST tensor: its values are checked here
     (ascending from offsets[0] >= 0 to offsets[V] <= len(point)), which the kernels rely on for their reads of ``point``."""
