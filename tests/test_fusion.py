@@ -12,7 +12,11 @@ DEV = "cuda"
 
 
 def _scene(h=96, w=128, n_views=5, seed=0, noise=0.0):
-    """a tilted plane seen by cameras on an arc: per view (K, E, depth map, confidence)"""
+    """a tilted plane seen by cameras on an arc: per view (K, E, depth map, confidence).
+    What it cannot detect: every view shares ONE K (fx == fy, no skew) and the cameras turn about the y axis only, so K_src <-> K_ref
+    (with their inverses) can be swapped in a pair block, or a ``cam`` block built from another view's K, without one changed output
+    bit; 24 of a pair block's 60 floats are exact zeros; a plane has no depth edge and no point behind a camera.
+    tests/fusion_scenes.py:general_scene is the scene without these blind spots (tests/test_fusion_scenes_cpu.py records them)."""
     rng = np.random.default_rng(seed)
     k = np.array([[1.2 * w, 0, w / 2 + 1.3], [0, 1.2 * w, h / 2 - 0.7], [0, 0, 1]], np.float32)
     normal, offset = np.array([0.1, -0.05, 1.0]), 700.0          # plane n.X = offset in world coordinates
