@@ -13,7 +13,7 @@
 //             finalize dbeta = sum g, dgamma = sum g * xhat, per-channel coefficients
 //             apply    dx = gamma * invstd * (g - mean(g) - xhat * mean(g * xhat))
 // 3 passes over the tensor forward, 5 backward; no atomics, results independent of the launch geometry's timing.
-#include "common.hpp"
+#include "wave_ops.hpp"
 
 namespace itermvs {
 
@@ -34,15 +34,9 @@ struct BnArgs {
     int N, C, HW, parts, relu, vec;
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // sum over the workgroup, returned to every thread (red: 4 floats of LDS per call site, guarded by the barriers inside)
 __device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
+    v = wave_sum_all(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();

@@ -24,6 +24,7 @@
 // (offsets 32, 16, ..., 1: every lane ends with the same bits), the 4 waves are added in wave order, and a single workgroup adds
 // the partials in ascending g.  umeyama_groups(n) below is the grid size.
 #include "cloud_grid.hpp"
+#include "wave_ops.hpp"
 
 namespace itermvs {
 
@@ -184,12 +185,6 @@ __global__ void __launch_bounds__(kCloudBlock) cloud_nn_index_kernel(const float
     d2[i] = hit ? best.d2 : INFINITY;
 }
 
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
-    return x;
-}
-
 __global__ void __launch_bounds__(kCloudBlock) cloud_umeyama_partial_kernel(const float* __restrict__ q, long long n, Transform T,
                                                                             const long long* __restrict__ idx,
                                                                             const double* __restrict__ d2,
@@ -220,7 +215,7 @@ __global__ void __launch_bounds__(kCloudBlock) cloud_umeyama_partial_kernel(cons
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < kSums; ++k) {
-        const double w = wave_sum(s[k]);
+        const double w = wave_sum_all(s[k]);
         if (lane == 0) s_part[wave][k] = w;
     }
     __syncthreads();

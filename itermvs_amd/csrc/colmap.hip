@@ -23,7 +23,7 @@
 // [-1, 1] here), and an image without a valid observation raises IndexError there (its range is NaN here; the host raises).
 #include <math.h>
 
-#include "common.hpp"
+#include "wave_ops.hpp"
 
 namespace itermvs {
 
@@ -81,7 +81,7 @@ __global__ void __launch_bounds__(kScoreBlock) view_scores_kernel(const int64_t*
                 if (p >= 0 && p < P && rel >= 0 && rel < chunk_bits && ((bitmap[rel >> 5] >> (rel & 31)) & 1u))
                     acc = acc + score_term(xyz, p, cix, ciy, ciz, cjx, cjy, cjz, theta0, den1, den2);
             }
-            for (int d = 32; d > 0; d >>= 1) acc = acc + __shfl_down(acc, d, 64);
+            acc = wave_sum_lane0(acc);
             if (lane == 0) {                               // the same lane of the same wave owns the pair in every chunk
                 const size_t a = (size_t)i * V + j, b = (size_t)j * V + i;
                 const double total = base ? score[a] + acc : acc;

@@ -8,14 +8,16 @@
 //   emit  : every workgroup recomputes its lanes' ranks and stores the records whose vertex index is below `capacity`.
 // Ordering comes from the stream alone: no workgroup waits on another, no atomics, so the bytes do not depend on scheduling.
 // Arithmetic: oracle/fusion_oracle.py:unproject_points -- pixel indices as float64, float32 matrices upcast, k-ascending products
-// and sums, each rounded once (-ffp-contract=off), one round-to-nearest conversion to float32 at the end.
+// and sums, each rounded once (cam_math.hpp), one round-to-nearest conversion to float32 at the end.
 // itermvs_fuse_points_normals: the same three launches with an emit kernel that writes 27-byte records (x, y, z, nx, ny, nz
 // float32, red, green, blue uint8).  Count, scan, the vertex index, the coordinates and the colour are the code of the 15-byte
 // path; the normal is the cross product of depth_avg's camera-space differences along the row and the column, turned towards
 // the camera and rotated to world space (definition: include/itermvs_hip.h; numpy restatement: tests/fuse_normals_reference.py).
 #include <cmath>
 
-#include "common.hpp"
+#include "cam_math.hpp"
+#include "flat_launch.hpp"
+#include "wave_ops.hpp"
 
 namespace itermvs {
 
@@ -24,28 +26,6 @@ constexpr int kPtsWaves = kPtsBlock / 64;
 constexpr int kScanBlock = 1024;
 constexpr int kRecordBytes = 15;
 constexpr int kNormalRecordBytes = 27;         // x y z | nx ny nz | red green blue
-
-// the same two products as fusion.hip (kept there untouched): (3x3 | rows 0..2 of 4x4, float32 upcast) @ float64 point
-__device__ __forceinline__ void pts_mat3(const float* __restrict__ m, double x, double y, double z, double& ox, double& oy,
-                                         double& oz) {
-    ox = ((double)m[0] * x + (double)m[1] * y) + (double)m[2] * z;
-    oy = ((double)m[3] * x + (double)m[4] * y) + (double)m[5] * z;
-    oz = ((double)m[6] * x + (double)m[7] * y) + (double)m[8] * z;
-}
-__device__ __forceinline__ void pts_mat34(const float* __restrict__ m, double x, double y, double z, double& ox, double& oy,
-                                          double& oz) {
-    ox = (((double)m[0] * x + (double)m[1] * y) + (double)m[2] * z) + (double)m[3] * 1.0;
-    oy = (((double)m[4] * x + (double)m[5] * y) + (double)m[6] * z) + (double)m[7] * 1.0;
-    oz = (((double)m[8] * x + (double)m[9] * y) + (double)m[10] * z) + (double)m[11] * 1.0;
-}
-
-// lanes of this wave below the caller with `on` set, and the wave's total
-__device__ __forceinline__ uint32_t wave_rank(bool on, uint32_t& total) {
-    const unsigned long long b = __ballot(on);
-    total = (uint32_t)__popcll(b);
-    const int lane = threadIdx.x & 63;
-    return (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-}
 
 // workspace: uint32 [3][nblocks] = final | photo | geo populations per workgroup
 __global__ void __launch_bounds__(kPtsBlock) fuse_points_count_kernel(const uint8_t* __restrict__ final_mask,
@@ -76,40 +56,15 @@ __global__ void __launch_bounds__(kPtsBlock) fuse_points_count_kernel(const uint
 __global__ void __launch_bounds__(kScanBlock) fuse_points_scan_kernel(uint32_t* __restrict__ ws, uint32_t nblocks, int has_photo,
                                                                       int has_geo, unsigned long long* __restrict__ cursor,
                                                                       long long* __restrict__ view_row) {
-    __shared__ uint32_t wave_sum[kScanBlock / 64];
     __shared__ unsigned long long red[2][kScanBlock / 64];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint32_t carry = 0;                                    // uniform: vertices of the chunks before this one
-    unsigned long long sp = 0, sg = 0;
-    for (uint32_t base = 0; base < nblocks; base += kScanBlock) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t v = i < nblocks ? ws[i] : 0u;
-        if (i < nblocks) {
-            sp += ws[(size_t)nblocks + i];
-            sg += ws[(size_t)2 * nblocks + i];
-        }
-        uint32_t inc = v;                                  // inclusive scan inside the wave
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += up;
-        }
-        if (lane == 63) wave_sum[wv] = inc;
-        __syncthreads();
-        uint32_t before = 0, chunk = 0;
-        for (int k = 0; k < kScanBlock / 64; ++k) {
-            const uint32_t s = wave_sum[k];
-            before += k < wv ? s : 0u;
-            chunk += s;
-        }
-        if (i < nblocks) ws[i] = carry + before + (inc - v);
-        carry += chunk;
-        __syncthreads();                                   // wave_sum is rewritten by the next chunk
-    }
-    for (int d = 32; d > 0; d >>= 1) {
-        sp += __shfl_down(sp, d, 64);
-        sg += __shfl_down(sg, d, 64);
-    }
-    if (lane == 0) { red[0][wv] = sp; red[1][wv] = sg; }
+    unsigned long long sp = 0, sg = 0;                     // the photo / geo rows are only summed, beside the scan's own loads
+    const uint32_t total = block_scan_exclusive_chunked<uint32_t, kScanBlock>(ws, nblocks, [&](uint32_t i) {
+        sp += ws[(size_t)nblocks + i];
+        sg += ws[(size_t)2 * nblocks + i];
+    });
+    sp = wave_sum_lane0(sp);
+    sg = wave_sum_lane0(sg);
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sp; red[1][threadIdx.x >> 6] = sg; }
     __syncthreads();
     if (threadIdx.x == 0) {
         unsigned long long tp = 0, tg = 0;
@@ -117,36 +72,24 @@ __global__ void __launch_bounds__(kScanBlock) fuse_points_scan_kernel(uint32_t* 
         const unsigned long long first = *cursor;
         view_row[0] = has_photo ? (long long)tp : -1;
         view_row[1] = has_geo ? (long long)tg : -1;
-        view_row[2] = (long long)carry;
+        view_row[2] = (long long)total;
         view_row[3] = (long long)first;
-        *cursor = first + carry;
+        *cursor = first + total;
     }
 }
 
 // the vertex index of this lane's pixel: the view's first vertex + the workgroups before it (scan) + the waves and lanes before it
 __device__ __forceinline__ unsigned long long pts_vertex_index(bool on, const uint32_t* __restrict__ ws,
                                                                const long long* __restrict__ view_row) {
-    __shared__ uint32_t part[kPtsWaves];
     uint32_t total;
-    const uint32_t rank = wave_rank(on, total);
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) part[wv] = total;
-    __syncthreads();
-    uint32_t before = 0;
-    for (int k = 0; k < kPtsWaves; ++k) before += k < wv ? part[k] : 0u;
-    return (unsigned long long)view_row[3] + ws[blockIdx.x] + before + rank;
+    const uint32_t own = on ? 1u : 0u, rank = wave_rank(on, total);
+    return (unsigned long long)view_row[3] + ws[blockIdx.x] + block_exclusive<kPtsWaves>(rank + own, own);
 }
 
 // camera-space point of pixel (x, y) at depth d (eval.py:291-292)
 __device__ __forceinline__ void pts_camera(const float* __restrict__ cam, uint32_t x, uint32_t y, double d, double& rx, double& ry,
                                            double& rz) {
-    pts_mat3(cam, (double)x * d, (double)y * d, d, rx, ry, rz);
-}
-
-// the records are not padded: no alignment to rely on, byte stores
-__device__ __forceinline__ void pts_put_f32(uint8_t* __restrict__ o, float v) {
-    const uint32_t b = __float_as_uint(v);
-    o[0] = (uint8_t)b; o[1] = (uint8_t)(b >> 8); o[2] = (uint8_t)(b >> 16); o[3] = (uint8_t)(b >> 24);
+    mat3(cam, (double)x * d, (double)y * d, d, rx, ry, rz);
 }
 
 // the part of a vertex record that both emit kernels write: world coordinates of the camera-space point (eval.py:293-294)
@@ -155,8 +98,8 @@ __device__ __forceinline__ void pts_put_vertex(const float* __restrict__ cam, do
                                                  const uint8_t* __restrict__ rgb, uint32_t p, uint8_t* __restrict__ xyz,
                                                  uint8_t* __restrict__ colour) {
     double wx, wy, wz;
-    pts_mat34(cam + 9, rx, ry, rz, wx, wy, wz);
-    pts_put_f32(xyz, (float)wx); pts_put_f32(xyz + 4, (float)wy); pts_put_f32(xyz + 8, (float)wz);
+    mat34(cam + 9, rx, ry, rz, wx, wy, wz);
+    put_f32_bytes(xyz, (float)wx); put_f32_bytes(xyz + 4, (float)wy); put_f32_bytes(xyz + 8, (float)wz);
     const uint8_t* c = rgb + (size_t)p * 3;
     colour[0] = c[0]; colour[1] = c[1]; colour[2] = c[2];
 }
@@ -212,10 +155,8 @@ __device__ __forceinline__ void pts_normal(const double* __restrict__ depth_avg,
     double nc[3] = {tx[1] * ty[2] - tx[2] * ty[1], tx[2] * ty[0] - tx[0] * ty[2], tx[0] * ty[1] - tx[1] * ty[0]};
     const double s = (nc[0] * c[0] + nc[1] * c[1]) + nc[2] * c[2];
     if (s > 0.0) { nc[0] = -nc[0]; nc[1] = -nc[1]; nc[2] = -nc[2]; }       // towards the camera, the origin of camera space
-    const float* r = cam + 9;                                                 // rows 0..2 of inv(E_ref); its 3x3 part rotates
-    const double nx = ((double)r[0] * nc[0] + (double)r[1] * nc[1]) + (double)r[2] * nc[2];
-    const double ny = ((double)r[4] * nc[0] + (double)r[5] * nc[1]) + (double)r[6] * nc[2];
-    const double nz = ((double)r[8] * nc[0] + (double)r[9] * nc[1]) + (double)r[10] * nc[2];
+    double nx, ny, nz;
+    rot34(cam + 9, nc[0], nc[1], nc[2], nx, ny, nz);                          // rows 0..2 of inv(E_ref); its 3x3 part rotates
     const double len = sqrt((nx * nx + ny * ny) + nz * nz);
     if (!(std::isfinite(len) && len > 0.0)) return;
     out[0] = (float)(nx / len); out[1] = (float)(ny / len); out[2] = (float)(nz / len);
@@ -238,7 +179,7 @@ __global__ void __launch_bounds__(kPtsBlock) fuse_points_normals_emit_kernel(
     pts_normal(depth_avg, cam, p, x, y, W, n, d, edge_thres, c, nrm);
     uint8_t* o = records + idx * kNormalRecordBytes;
     pts_put_vertex(cam, c[0], c[1], c[2], rgb, p, o, o + 24);
-    pts_put_f32(o + 12, nrm[0]); pts_put_f32(o + 16, nrm[1]); pts_put_f32(o + 20, nrm[2]);
+    put_f32_bytes(o + 12, nrm[0]); put_f32_bytes(o + 16, nrm[1]); put_f32_bytes(o + 20, nrm[2]);
 }
 
 // H*W <= this keeps every 32-bit pixel index, workgroup count and relative offset in range
@@ -254,57 +195,43 @@ extern "C" int itermvs_fuse_points_workspace_bytes(int32_t H, int32_t W) {
     return (int)(3 * nblocks * (long long)sizeof(uint32_t));
 }
 
-// the argument checks that both entry points make, in this order, before anything is launched
-static int fuse_points_check(const double* depth_avg, const uint8_t* final_mask, const float* cam, const uint8_t* rgb, int32_t H,
-                             int32_t W, const uint8_t* records, int64_t capacity, const uint64_t* cursor, const int64_t* view_counts,
-                             int32_t view, const uint32_t* workspace) {
+// both entry points: the argument checks, in this order, before anything is launched, then count, scan and the emit kernel of the
+// record format -- normals false: 15-byte records, edge_thres not used; true: 27-byte records
+static int fuse_points_run(const double* depth_avg, const uint8_t* final_mask, const uint8_t* photo_mask, const uint8_t* geo_mask,
+                           const float* cam, const uint8_t* rgb, int32_t H, int32_t W, bool normals, double edge_thres, uint8_t* records,
+                           int64_t capacity, uint64_t* cursor, int64_t* view_counts, int32_t view, uint32_t* workspace, void* stream) {
     ITERMVS_RETURN_IF(!depth_avg || !final_mask || !cam || !rgb || !cursor || !view_counts || !workspace, ITERMVS_ERR_NULL);
     ITERMVS_RETURN_IF(!records && capacity != 0, ITERMVS_ERR_NULL);
     ITERMVS_RETURN_IF(H < 1 || W < 1 || (long long)H * W > kPtsMaxPixels || capacity < 0 || view < 0, ITERMVS_ERR_DIMS);
-    return ITERMVS_OK;
-}
-
-// the first two launches of both entry points -> the view's row of view_counts, which the emit kernel reads
-static const long long* fuse_points_count_and_scan(const uint8_t* final_mask, const uint8_t* photo_mask, const uint8_t* geo_mask,
-                                                   uint32_t n, uint32_t nblocks, uint64_t* cursor, int64_t* view_counts,
-                                                   int32_t view, uint32_t* workspace, hipStream_t s) {
-    long long* row = (long long*)view_counts + (size_t)view * 4;
-    hipLaunchKernelGGL(fuse_points_count_kernel, dim3(nblocks), dim3(kPtsBlock), 0, s, final_mask, photo_mask, geo_mask, n,
-                       workspace);
+    ITERMVS_RETURN_IF(normals && (!std::isfinite(edge_thres) || !(edge_thres > 0.0)), ITERMVS_ERR_DIMS);
+    const FlatItems items{(int64_t)H * W, kPtsMaxPixels};
+    const uint32_t n = (uint32_t)items.total, nblocks = (n + kPtsBlock - 1) / kPtsBlock;
+    hipStream_t s = (hipStream_t)stream;
+    long long* row = (long long*)view_counts + (size_t)view * 4;     // the scan fills it, the emit kernel reads it
+    const int bad = flat_launch<fuse_points_count_kernel, kPtsBlock>(items, s, final_mask, photo_mask, geo_mask, n, workspace);
+    if (bad != ITERMVS_OK) return bad;
     hipLaunchKernelGGL(fuse_points_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, workspace, nblocks, photo_mask ? 1 : 0,
                        geo_mask ? 1 : 0, (unsigned long long*)cursor, row);
-    return row;
+    if (!normals)
+        return flat_launch<fuse_points_emit_kernel, kPtsBlock>(items, s, depth_avg, final_mask, cam, rgb, n, (uint32_t)W, workspace,
+                                                               (const long long*)row, records, (unsigned long long)capacity);
+    return flat_launch<fuse_points_normals_emit_kernel, kPtsBlock>(items, s, depth_avg, final_mask, cam, rgb, n, (uint32_t)W,
+                                                                   edge_thres, workspace, (const long long*)row, records,
+                                                                   (unsigned long long)capacity);
 }
 
 extern "C" int itermvs_fuse_points(const double* depth_avg, const uint8_t* final_mask, const uint8_t* photo_mask,
                                    const uint8_t* geo_mask, const float* cam, const uint8_t* rgb, int32_t H, int32_t W,
                                    uint8_t* records, int64_t capacity, uint64_t* cursor, int64_t* view_counts, int32_t view,
                                    uint32_t* workspace, void* stream) {
-    const int bad = fuse_points_check(depth_avg, final_mask, cam, rgb, H, W, records, capacity, cursor, view_counts, view, workspace);
-    if (bad != ITERMVS_OK) return bad;
-    const uint32_t n = (uint32_t)((long long)H * W);
-    const uint32_t nblocks = (n + kPtsBlock - 1) / kPtsBlock;
-    hipStream_t s = (hipStream_t)stream;
-    const long long* row = fuse_points_count_and_scan(final_mask, photo_mask, geo_mask, n, nblocks, cursor, view_counts, view,
-                                                      workspace, s);
-    hipLaunchKernelGGL(fuse_points_emit_kernel, dim3(nblocks), dim3(kPtsBlock), 0, s, depth_avg, final_mask, cam, rgb, n,
-                       (uint32_t)W, workspace, row, records, (unsigned long long)capacity);
-    return itermvs_launch_status();
+    return fuse_points_run(depth_avg, final_mask, photo_mask, geo_mask, cam, rgb, H, W, false, 0.0, records, capacity, cursor,
+                           view_counts, view, workspace, stream);
 }
 
 extern "C" int itermvs_fuse_points_normals(const double* depth_avg, const uint8_t* final_mask, const uint8_t* photo_mask,
                                            const uint8_t* geo_mask, const float* cam, const uint8_t* rgb, int32_t H, int32_t W,
                                            double edge_thres, uint8_t* records, int64_t capacity, uint64_t* cursor,
                                            int64_t* view_counts, int32_t view, uint32_t* workspace, void* stream) {
-    const int bad = fuse_points_check(depth_avg, final_mask, cam, rgb, H, W, records, capacity, cursor, view_counts, view, workspace);
-    if (bad != ITERMVS_OK) return bad;
-    ITERMVS_RETURN_IF(!std::isfinite(edge_thres) || !(edge_thres > 0.0), ITERMVS_ERR_DIMS);
-    const uint32_t n = (uint32_t)((long long)H * W);
-    const uint32_t nblocks = (n + kPtsBlock - 1) / kPtsBlock;
-    hipStream_t s = (hipStream_t)stream;
-    const long long* row = fuse_points_count_and_scan(final_mask, photo_mask, geo_mask, n, nblocks, cursor, view_counts, view,
-                                                      workspace, s);
-    hipLaunchKernelGGL(fuse_points_normals_emit_kernel, dim3(nblocks), dim3(kPtsBlock), 0, s, depth_avg, final_mask, cam, rgb, n,
-                       (uint32_t)W, edge_thres, workspace, row, records, (unsigned long long)capacity);
-    return itermvs_launch_status();
+    return fuse_points_run(depth_avg, final_mask, photo_mask, geo_mask, cam, rgb, H, W, true, edge_thres, records, capacity, cursor,
+                           view_counts, view, workspace, stream);
 }

@@ -4,14 +4,14 @@
 // views and keeps the consistency count and the depth sum in registers; no per-view reprojection maps or masks
 // ever reach memory (the reference materialises six [H,W] float64/float32 arrays per pair).
 // Arithmetic mirrors numpy's promotion rules in the reference: pixel grid int64, depths float32, camera matrices
-// float32 (inverted / composed on the host exactly like eval.py does), every product with a point in float64;
+// float32 (inverted / composed on the host exactly like eval.py does), every product with a point in float64 (cam_math.hpp);
 // cv2.remap(INTER_LINEAR) as published (1/32-pixel coordinates, float32 weights, zero border).  oracle/fusion_oracle.py
 // is the CPU restatement the tests compare against, bit for bit.
 // itermvs_fuse_depth_claim is the same per-pixel body (fuse_pixel<true>) with the claim step of include/itermvs_hip.h behind it:
 // a pixel that another view's emitted point was verified against is marked and never emits a copy of that point.
 #include <math.h>
 
-#include "common.hpp"
+#include "cam_math.hpp"
 
 namespace itermvs {
 
@@ -29,19 +29,6 @@ struct FuseArgs {
     double geo_pixel_thres;
     float geo_depth_thres, photo_thres;
 };
-
-__device__ __forceinline__ void mat3(const float* __restrict__ m, double x, double y, double z, double& ox, double& oy,
-                                     double& oz) {
-    ox = ((double)m[0] * x + (double)m[1] * y) + (double)m[2] * z;
-    oy = ((double)m[3] * x + (double)m[4] * y) + (double)m[5] * z;
-    oz = ((double)m[6] * x + (double)m[7] * y) + (double)m[8] * z;
-}
-__device__ __forceinline__ void mat34(const float* __restrict__ m, double x, double y, double z, double& ox, double& oy,
-                                      double& oz) {
-    ox = (((double)m[0] * x + (double)m[1] * y) + (double)m[2] * z) + (double)m[3] * 1.0;
-    oy = (((double)m[4] * x + (double)m[5] * y) + (double)m[6] * z) + (double)m[7] * 1.0;
-    oz = (((double)m[8] * x + (double)m[9] * y) + (double)m[10] * z) + (double)m[11] * 1.0;
-}
 
 __device__ __forceinline__ long long remap_fixed(float c) {   // cvRound(c * 32) with saturate_cast<int>
     const double v = (double)c * 32.0;

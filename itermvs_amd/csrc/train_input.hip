@@ -14,6 +14,7 @@
 //    restated from OpenCV's source (unpinned, like image.hip's bilinear resize).
 #include "flat_launch.hpp"
 #include "image_level0.hpp"
+#include "wave_ops.hpp"
 
 namespace itermvs {
 
@@ -48,7 +49,7 @@ __global__ void __launch_bounds__(256) jitter_lsum_kernel(const uint8_t* __restr
         }
         acc += (unsigned long long)pil_l(r, g, b);
     }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    acc = wave_sum_lane0(acc);
     __shared__ unsigned long long part[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) part[wave] = acc;

@@ -14,9 +14,10 @@
 // Ordering comes from the stream alone: no workgroup waits on another, no atomics, so the bytes do not depend on scheduling.
 #include <cmath>
 
-#include "common.hpp"
+#include "cam_math.hpp"
 #include "flat_launch.hpp"
 #include "tsdf_tets.hpp"
+#include "wave_ops.hpp"
 
 namespace itermvs {
 
@@ -66,9 +67,10 @@ __global__ void __launch_bounds__(kTsdfBlock) tsdf_integrate_kernel(uint32_t* __
     for (int v = 0; v < V && s.count < kTsdfMaxCount; ++v) {
         const float* __restrict__ k = cams + (size_t)v * 21;
         const float* __restrict__ e = k + 9;
-        const double px = (((double)e[0] * cx + (double)e[1] * cy) + (double)e[2] * cz) + (double)e[3];
-        const double py = (((double)e[4] * cx + (double)e[5] * cy) + (double)e[6] * cz) + (double)e[7];
-        const double pz = (((double)e[8] * cx + (double)e[9] * cy) + (double)e[10] * cz) + (double)e[11];
+        // mat34(e, ...) of cam_math.hpp spelled out: profiles/wave_ops/README.md has what the inlined call cost this kernel
+        const double px = (((double)e[0] * cx + (double)e[1] * cy) + (double)e[2] * cz) + (double)e[3] * 1.0;
+        const double py = (((double)e[4] * cx + (double)e[5] * cy) + (double)e[6] * cz) + (double)e[7] * 1.0;
+        const double pz = (((double)e[8] * cx + (double)e[9] * cy) + (double)e[10] * cz) + (double)e[11] * 1.0;
         if (!(std::isfinite(pz) && pz > 0.0)) continue;
         const double ux = (((double)k[0] * px + (double)k[1] * py) + (double)k[2] * pz) / pz;
         const double uy = (((double)k[3] * px + (double)k[4] * py) + (double)k[5] * pz) / pz;
@@ -145,11 +147,8 @@ __global__ void __launch_bounds__(kTsdfBlock) tsdf_count_kernel(const uint8_t* _
                                                                 uint32_t n, unsigned long long* __restrict__ counts) {
     __shared__ uint32_t part[2][kTsdfWaves];
     const uint32_t idx = blockIdx.x * kTsdfBlock + threadIdx.x;
-    uint32_t nv = idx < n ? tsdf_marks_of(marks, idx, kTsdfDirs) : 0u, nf = idx < n ? cell_faces[idx] : 0u;
-    for (int d = 32; d > 0; d >>= 1) {
-        nv += __shfl_down(nv, d, 64);
-        nf += __shfl_down(nf, d, 64);
-    }
+    const uint32_t nv = wave_sum_lane0(idx < n ? tsdf_marks_of(marks, idx, kTsdfDirs) : 0u);
+    const uint32_t nf = wave_sum_lane0(idx < n ? (uint32_t)cell_faces[idx] : 0u);
     if ((threadIdx.x & 63) == 0) { part[0][threadIdx.x >> 6] = nv; part[1][threadIdx.x >> 6] = nf; }
     __syncthreads();
     if (threadIdx.x < 2) {
@@ -162,55 +161,17 @@ __global__ void __launch_bounds__(kTsdfBlock) tsdf_count_kernel(const uint8_t* _
 // one workgroup: both rows of counts -> exclusive offsets in place; totals[0] = vertices, totals[1] = triangles
 __global__ void __launch_bounds__(kTsdfScanBlock) tsdf_scan_kernel(unsigned long long* __restrict__ counts, uint32_t nblocks,
                                                                    unsigned long long* __restrict__ totals) {
-    __shared__ unsigned long long wave_sum[kTsdfScanBlock / 64];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     for (int row = 0; row < 2; ++row) {
-        unsigned long long* c = counts + (size_t)row * nblocks;
-        unsigned long long carry = 0;                                  // uniform: the chunks before this one
-        for (uint32_t base = 0; base < nblocks; base += kTsdfScanBlock) {
-            const uint32_t i = base + threadIdx.x;
-            const unsigned long long v = i < nblocks ? c[i] : 0ull;
-            unsigned long long inc = v;
-            for (int d = 1; d < 64; d <<= 1) {
-                const unsigned long long up = __shfl_up(inc, d, 64);
-                if (lane >= d) inc += up;
-            }
-            if (lane == 63) wave_sum[wv] = inc;
-            __syncthreads();
-            unsigned long long before = 0, chunk = 0;
-            for (int k = 0; k < kTsdfScanBlock / 64; ++k) {
-                const unsigned long long s = wave_sum[k];
-                before += k < wv ? s : 0ull;
-                chunk += s;
-            }
-            if (i < nblocks) c[i] = carry + before + (inc - v);
-            carry += chunk;
-            __syncthreads();                                           // wave_sum is rewritten by the next chunk
-        }
-        if (threadIdx.x == 0) totals[row] = carry;
+        const auto total = block_scan_exclusive_chunked<unsigned long long, kTsdfScanBlock>(counts + (size_t)row * nblocks, nblocks, [](uint32_t) {});
+        if (threadIdx.x == 0) totals[row] = total;
     }
 }
 
-// v items of this thread -> the items of the workgroup's threads before it; every thread of the workgroup calls it
+// v items of this thread -> the items of the workgroup's threads before it; every thread of the workgroup calls it, once per kernel
 __device__ __forceinline__ uint32_t tsdf_block_rank(uint32_t v) {
-    __shared__ uint32_t part[kTsdfWaves];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint32_t inc = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += up;
-    }
-    if (lane == 63) part[wv] = inc;
-    __syncthreads();
-    uint32_t before = 0;
-    for (int k = 0; k < kTsdfWaves; ++k) before += k < wv ? part[k] : 0u;
-    return before + (inc - v);
+    return block_exclusive<kTsdfWaves>(wave_inclusive_scan(v), v);
 }
 
-__device__ __forceinline__ void tsdf_put_f32(uint8_t* __restrict__ o, float v) {       // the records are not padded: byte stores
-    const uint32_t b = __float_as_uint(v);
-    o[0] = (uint8_t)b; o[1] = (uint8_t)(b >> 8); o[2] = (uint8_t)(b >> 16); o[3] = (uint8_t)(b >> 24);
-}
 __device__ __forceinline__ uint8_t tsdf_colour(uint32_t sa, uint32_t na, uint32_t sb, uint32_t nb, double s) {
     const double a = (double)sa / (double)na, b = (double)sb / (double)nb;
     return (uint8_t)fmin(255.0, fmax(0.0, rint(a + s * (b - a))));
@@ -245,9 +206,9 @@ __global__ void __launch_bounds__(kTsdfBlock) tsdf_vertex_kernel(const uint32_t*
         const double ya = tsdf_centre(g.oy, iy, g.voxel), yb = tsdf_centre(g.oy, iy + ((bits >> 1) & 1), g.voxel);
         const double za = tsdf_centre(g.oz, iz, g.voxel), zb = tsdf_centre(g.oz, iz + (bits >> 2), g.voxel);
         uint8_t* o = vertices + at * kMeshVertexBytes;
-        tsdf_put_f32(o, (float)(xa + s * (xb - xa)));
-        tsdf_put_f32(o + 4, (float)(ya + s * (yb - ya)));
-        tsdf_put_f32(o + 8, (float)(za + s * (zb - za)));
+        put_f32_bytes(o, (float)(xa + s * (xb - xa)));
+        put_f32_bytes(o + 4, (float)(ya + s * (yb - ya)));
+        put_f32_bytes(o + 8, (float)(za + s * (zb - za)));
         o[12] = tsdf_colour(a.r, a.count, b.r, b.count, s);
         o[13] = tsdf_colour(a.g, a.count, b.g, b.count, s);
         o[14] = tsdf_colour(a.b, a.count, b.b, b.count, s);
