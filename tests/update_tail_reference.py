@@ -38,11 +38,14 @@ def first_argmax(prob: torch.Tensor) -> torch.Tensor:
     return torch.where(prob == top, idx, torch.full_like(idx, k)).amin(dim=1, keepdim=True)
 
 
-def window_regression(prob: torch.Tensor, radius: int = RADIUS) -> Tuple[torch.Tensor, torch.Tensor]:
+def window_regression(prob: torch.Tensor, radius: int = RADIUS, best=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """prob [B,K,H,W] -> (normalised depth [B,1,H,W] in prob's dtype, arg-max int64 [B,1,H,W]).  The window indices are
-    clamped to [0, K-1]; a clamped index appears (and is counted) more than once; the denominator starts at 1e-6."""
+    clamped to [0, K-1]; a clamped index appears (and is counted) more than once; the denominator starts at 1e-6.
+    ``best`` (int64 [B,1,H,W]): centre the window there instead of on the first arg-max (tests/head_reference.py asks what
+    the regression would be around the runner-up of a near-tie)."""
     k = prob.shape[1]
-    best = first_argmax(prob)
+    if best is None:
+        best = first_argmax(prob)
     num = torch.zeros_like(prob[:, :1])
     den = torch.full_like(prob[:, :1], 1e-6)
     for off in range(-radius, radius + 1):
