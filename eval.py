@@ -36,6 +36,14 @@ from itermvs_amd.data_io import save_pfm  # noqa: E402
 from itermvs_amd.net import Pipeline  # noqa: E402
 
 
+class _StoreGiven(argparse.Action):
+    """store, and note on the namespace that the flag was given (``<dest>_given``): a default cannot be told from a typed value"""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values)
+        setattr(namespace, self.dest + "_given", True)
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Predict depth maps (MI355X engine)")
     p.add_argument("--model", default="IterMVS")
@@ -72,9 +80,26 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--geo_pixel_thres", type=float, default=1)
     p.add_argument("--geo_depth_thres", type=float, default=0.01)
     p.add_argument("--photo_thres", type=float, default=0.3)
-    p.add_argument("--geo_mask_thres", type=int, default=3,
+    p.add_argument("--geo_mask_thres", type=int, default=3, action=_StoreGiven,
                    help="--filter: source views that must agree with a reference pixel (eval.py:323-324: the reference fuses DTU "
                         "with 4 and everything else with 3; the default 3 keeps this driver's clouds as they were)")
+    p.add_argument("--geo_consistency", default="static", choices=["static", "dynamic"],
+                   help="--filter: how the source views decide a reference pixel's geometric mask.  static (default): at least "
+                        "--geo_mask_thres of them reproject within --geo_pixel_thres and --geo_depth_thres; every byte as before.  "
+                        "dynamic: dynamic consistency checking (D2HC-RMVSNet) -- a source passes level n when it reprojects within "
+                        "n * --dyn_pixel_step pixels and n * --dyn_depth_step of relative depth, and the pixel is kept at the "
+                        "smallest level n of --dyn_levels that at least n sources pass: few views that agree tightly or many that "
+                        "agree loosely, with no per-scene count (itermvs_fuse_depth_dynamic).  --geo_mask_thres must then not be "
+                        "given; the depth average still uses --geo_pixel_thres and --geo_depth_thres")
+    p.add_argument("--dyn_pixel_step", type=float, default=None,
+                   help="--geo_consistency dynamic: pixels of reprojection error allowed per level (default 0.25; from memory of "
+                        "the published code, unverified)")
+    p.add_argument("--dyn_depth_step", type=float, default=None,
+                   help="--geo_consistency dynamic: relative depth difference allowed per level, rounded to float32 (default "
+                        "1/1300; from memory of the published code, unverified)")
+    p.add_argument("--dyn_levels", type=int, nargs=2, default=None, metavar=("MIN", "MAX"),
+                   help="--geo_consistency dynamic: the levels that are tried, 1 <= MIN <= MAX <= 16 (default 2 10; from memory of "
+                        "the published code, unverified); levels above the number of source views cannot accept")
     p.add_argument("--num_samples", type=int, default=8, help="synthetic dataset: number of reference views")
     p.add_argument("--filter", action="store_true", help="fuse the saved depth maps of every scan into a point cloud (eval.py:311-325)")
     p.add_argument("--fuse_points", default="host", choices=["host", "device"],
@@ -277,6 +302,33 @@ def check_mesh(args) -> bool:
     return True
 
 
+def check_geo_consistency(args) -> str:
+    """--geo_consistency dynamic needs --filter, takes no --geo_mask_thres and checks its --dyn_* values; the --dyn_* flags need
+    it.  What is refused is refused as an argparse error (usage, exit status 2), before any work."""
+    from itermvs_amd import fusion
+    mode = getattr(args, "geo_consistency", "static")
+    given = [flag for flag in ("dyn_pixel_step", "dyn_depth_step", "dyn_levels") if getattr(args, flag, None) is not None]
+    error = build_parser().error
+    if mode != "dynamic":
+        if given:
+            error("--{} needs --geo_consistency dynamic".format(given[0]))
+        return mode
+    if not args.filter:
+        error("--geo_consistency dynamic needs --filter (it is a rule of the fusion stage)")
+    if getattr(args, "geo_mask_thres_given", False):
+        error("--geo_mask_thres {} cannot be given with --geo_consistency dynamic: the level rule takes the place of the count "
+              "(see --dyn_levels)".format(args.geo_mask_thres))
+    rule = fusion.consistency_from_args(args)
+    problem = fusion.dynamic_problem(rule["dyn_pixel_step"], rule["dyn_depth_step"], rule["dyn_n_min"], rule["dyn_n_max"])
+    if problem == "steps":
+        error("--geo_consistency dynamic: --dyn_pixel_step and --dyn_depth_step (rounded to float32) must be finite and above 0, "
+              "got {} and {}".format(rule["dyn_pixel_step"], rule["dyn_depth_step"]))
+    if problem == "levels":
+        error("--geo_consistency dynamic: --dyn_levels MIN MAX must satisfy 1 <= MIN <= MAX <= 16, got {}..{}".format(
+            rule["dyn_n_min"], rule["dyn_n_max"]))
+    return mode
+
+
 def fuse_memory(args) -> dict:
     """--fuse_source memory: depth maps and point clouds in one pass (itermvs_amd.scan_fuse); scans are sharded over the
     ranks whole, like ``fuse_scans`` shards them.  -> {scan: {ref_view: (geo, photo, final mask share)}} of this rank"""
@@ -285,6 +337,7 @@ def fuse_memory(args) -> dict:
     check_fuse_dedupe(args)
     check_ply_normals(args)
     check_mesh(args)
+    check_geo_consistency(args)
     check_feature_cache(args)
     rank, local_rank, world = shard.init_distributed()
     torch.cuda.set_device(local_rank)
@@ -393,6 +446,7 @@ def fuse_scans(args) -> int:
     dedupe = check_fuse_dedupe(args)
     normals = check_ply_normals(args)
     check_mesh(args)
+    check_geo_consistency(args)
     rank, local_rank, world = shard.init_distributed()
     dev = "cuda:%d" % local_rank
     scans = sorted(d for d in os.listdir(args.testpath)
@@ -406,7 +460,8 @@ def fuse_scans(args) -> int:
                                     points=args.fuse_points,
                                     save_masks=args.save_masks, dedupe=dedupe, normals=normals,
                                     normal_edge_thres=getattr(args, "normal_edge_thres", 0.01),
-                                    mesh=fusion.mesh_options_from_args(args, os.path.join(args.outdir, scan + "_mesh.ply")))
+                                    mesh=fusion.mesh_options_from_args(args, os.path.join(args.outdir, scan + "_mesh.ply")),
+                                    **fusion.consistency_from_args(args))
         for v, (g, ph, f) in stats.items():
             print("processing {}, ref-view{:0>2}, geo_mask:{:3f} photo_mask:{:3f} final_mask: {:3f}".format(scan, v, g, ph, f))
         n += 1
@@ -420,6 +475,7 @@ if __name__ == "__main__":
     check_fuse_dedupe(a)
     check_ply_normals(a)
     check_mesh(a)
+    check_geo_consistency(a)
     if check_fuse_source(a) == "memory":
         fuse_memory(a)
     else:

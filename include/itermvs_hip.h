@@ -724,6 +724,35 @@ int itermvs_fuse_depth_claim(const float* depth_ref, const float* conf_ref, cons
                              const uint8_t* claimed_ref, uint8_t* const* claimed_src, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * itermvs_fuse_depth_dynamic -- itermvs_fuse_depth_claim with dynamic geometric consistency in place of the count against
+ *   geo_mask_thres (eval.py --geo_consistency dynamic): few source views that agree tightly are accepted, and so are many that
+ *   agree loosely, with no per-scene number (the dynamic consistency checking of D2HC-RMVSNet).  For one reference pixel p:
+ *   Per source s, unchanged from itermvs_fuse_depth (same expressions, same bits): dist_s fp64, the pixel distance of the
+ *     reprojection (eval.py:203); rel_s fp32, its relative depth difference (eval.py:205-206); ok_s = dist_s < geo_pixel_thres
+ *     && rel_s < geo_depth_thres, the base decision.
+ *   Levels: s passes level n iff dist_s < (double)n * dyn_pixel_step && rel_s < (float)n * dyn_depth_step -- each product
+ *     rounded once, the comparisons strict, NaN fails.  c_n = number of sources that pass level n.
+ *     level = the smallest n in [n_min, min(n_max, S)] with c_n >= n, or 0 if there is none.
+ *   Masks: geo = level != 0; photo = conf > photo_thres; final = photo && geo && claimed_ref[p] == 0.
+ *   depth_avg, the count geo_sum and the claim step (step 3 of itermvs_fuse_depth_claim) are bit for bit those of
+ *     itermvs_fuse_depth / itermvs_fuse_depth_claim on the same inputs: the average is taken over the sources with ok_s and the
+ *     claims are made for the sources with ok_s.  There is no geo_mask_thres.
+ *   The reference has no counterpart of the level rule (like step 3 of itermvs_fuse_depth_claim).  The driver's defaults,
+ *     dyn_pixel_step 0.25, dyn_depth_step (float)(1.0 / 1300), levels 2..10, are written from memory of the published code
+ *     and are UNVERIFIED.
+ * claimed_ref, claimed_src: as in itermvs_fuse_depth_claim, either may be NULL; both NULL is the form without the claim maps.
+ * geo_level: optional device [H,W] uint8, receives level.  No LDS, no atomics, one pass; the launch shape of itermvs_fuse_depth.
+ * Validation before any HIP call: the checks of itermvs_fuse_depth_claim in its order, then ITERMVS_ERR_DIMS unless
+ *   dyn_pixel_step and dyn_depth_step are finite and > 0 and 1 <= n_min <= n_max <= ITERMVS_MAX_SRC (n_max > S is allowed).
+ * ------------------------------------------------------------------------------------------ */
+int itermvs_fuse_depth_dynamic(const float* depth_ref, const float* conf_ref, const float* const* depth_src,
+                               const float* mats, int32_t S, int32_t H, int32_t W, double geo_pixel_thres,
+                               float geo_depth_thres, float photo_thres, double* depth_avg, uint8_t* photo_mask,
+                               uint8_t* geo_mask, uint8_t* final_mask, int32_t* geo_sum, const uint8_t* claimed_ref,
+                               uint8_t* const* claimed_src, double dyn_pixel_step, float dyn_depth_step, int32_t n_min,
+                               int32_t n_max, uint8_t* geo_level, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * itermvs_fuse_points -- the tail of filter_depth for ONE reference view (eval.py:287-308): the pixels of `final_mask` are
  *   unprojected (eval.py:287-294), coloured (eval.py:295-296) and appended to `records` as the PLY vertex element of
  *   eval.py:298-308 (x, y, z little-endian float32; red, green, blue uint8: 15 bytes per vertex, unpadded), in row-major pixel

@@ -9,6 +9,8 @@
 // is the CPU restatement the tests compare against, bit for bit.
 // itermvs_fuse_depth_claim is the same per-pixel body (fuse_pixel<true>) with the claim step of include/itermvs_hip.h behind it:
 // a pixel that another view's emitted point was verified against is marked and never emits a copy of that point.
+// itermvs_fuse_depth_dynamic is that body once more (fuse_pixel<true, true>) with the level rule of include/itermvs_hip.h in
+// place of the count against geo_mask_thres: the per-source errors are in registers already, so the rule costs no memory traffic.
 #include <math.h>
 
 #include "cam_math.hpp"
@@ -58,6 +60,13 @@ struct FuseClaimArgs {
     uint8_t* claimed_src[ITERMVS_MAX_SRC];       // [H,W] per source view; claimed_src[0] null: the claim step is skipped
 };
 
+struct FuseDynArgs {
+    double pixel_step;                           // a: a source passes level n iff dist < (double)n * a && rel < (float)n * b
+    float depth_step;                            // b
+    int n_min, n_max;
+    uint8_t* geo_level;                          // [H,W] or null
+};
+
 // reference pixel (px, py, d) = (x * d, y * d, d) -> its position in the source view of `m`, float64   (eval.py:162-169)
 __device__ __forceinline__ void project_to_source(const float* __restrict__ m, double px, double py, double d, double& xs,
                                                   double& ys) {
@@ -71,9 +80,13 @@ __device__ __forceinline__ void project_to_source(const float* __restrict__ m, d
 
 // One reference pixel.  Claim = false is itermvs_fuse_depth; Claim = true adds the two places where the claim maps enter: the
 // pixel's own mark gates `final`, and an emitting pixel marks the source pixel nearest to each consistent reprojection.
-template <bool Claim>
+// Dynamic = true replaces `geo`: a source's first passing level (thresholds grow with n, so it passes every level from there on)
+// is found by comparison in the source loop and counted in an 8-bit field of hist0 / hist1 (field i: level n_min + i, 16 fields
+// for at most ITERMVS_MAX_SRC levels); the running sum of the fields is c_n.  The average, the count and the claims stay those
+// of the base decision `ok`.
+template <bool Claim, bool Dynamic>
 __device__ __forceinline__ void fuse_pixel(const FuseArgs& a, const uint8_t* __restrict__ claimed_ref,
-                                           uint8_t* const* claimed_src) {
+                                           uint8_t* const* claimed_src, const FuseDynArgs* dyn) {
     const int x = blockIdx.x * 32 + (threadIdx.x & 31);
     const int y = blockIdx.y * 8 + (threadIdx.x >> 5);
     if (x >= a.W || y >= a.H) return;
@@ -84,6 +97,8 @@ __device__ __forceinline__ void fuse_pixel(const FuseArgs& a, const uint8_t* __r
     int geo = 0;
     uint32_t ok_bits = 0;
     float acc = 0.0f;
+    uint64_t hist0 = 0, hist1 = 0;
+    const int n_top = Dynamic ? (dyn->n_max < a.S ? dyn->n_max : a.S) : 0;                  // min(n_max, S)
     for (int s = 0; s < a.S; ++s) {
         const float* __restrict__ m = a.mats + s * 60;
         double xs, ys;
@@ -103,16 +118,35 @@ __device__ __forceinline__ void fuse_pixel(const FuseArgs& a, const uint8_t* __r
         geo += ok ? 1 : 0;
         if (Claim) ok_bits |= (ok ? 1u : 0u) << s;
         acc = acc + (ok ? drep : 0.0f);                                                     // eval.py:209,262
+        if (Dynamic) {
+            for (int n = dyn->n_min; n <= n_top; ++n) {
+                if (dist < (double)n * dyn->pixel_step && rel < (float)n * dyn->depth_step) {   // NaN fails every level
+                    const int i = n - dyn->n_min;
+                    if (i < 8) hist0 += 1ull << (8 * i); else hist1 += 1ull << (8 * (i - 8));
+                    break;
+                }
+            }
+        }
+    }
+    int level = 0;
+    if (Dynamic) {
+        int c = 0;
+        for (int n = dyn->n_min; n <= n_top; ++n) {
+            const int i = n - dyn->n_min;
+            c += (int)((i < 8 ? hist0 >> (8 * i) : hist1 >> (8 * (i - 8))) & 0xffu);
+            if (c >= n) { level = n; break; }
+        }
     }
     const float total = acc + dref;
     a.depth_avg[p] = (double)total / (double)(geo + 1);                                    // eval.py:264
-    const bool photo = a.conf_ref[p] > a.photo_thres, g = geo >= a.geo_mask_thres;
+    const bool photo = a.conf_ref[p] > a.photo_thres, g = Dynamic ? level != 0 : geo >= a.geo_mask_thres;
     bool final = photo && g;
     if (Claim) final = final && !(claimed_ref && claimed_ref[p] != 0);
     if (a.photo_mask) a.photo_mask[p] = photo;
     if (a.geo_mask) a.geo_mask[p] = g;
     if (a.final_mask) a.final_mask[p] = final;
     if (a.geo_sum) a.geo_sum[p] = geo;
+    if (Dynamic && dyn->geo_level) dyn->geo_level[p] = (uint8_t)level;
     if (!Claim || !final || !claimed_src[0]) return;
     // The claim step, for the few pixels that emit: the projection and the sample of each consistent source are computed again
     // by the expressions above (same operations, same bits) instead of being held in registers for all S sources.
@@ -131,13 +165,18 @@ __device__ __forceinline__ void fuse_pixel(const FuseArgs& a, const uint8_t* __r
 }
 
 __global__ void __launch_bounds__(256) fuse_depth_kernel(const FuseArgs a) {
-    fuse_pixel<false>(a, nullptr, nullptr);
+    fuse_pixel<false, false>(a, nullptr, nullptr, nullptr);
 }
 
 // Reads claimed_ref, writes claimed_src[s] (never the same map: checked on the host) with plain byte stores of the constant 1:
 // whichever threads reach a byte, in whatever order, it ends as 1, so the maps do not depend on scheduling and need no atomics.
 __global__ void __launch_bounds__(256) fuse_depth_claim_kernel(const FuseClaimArgs c) {
-    fuse_pixel<true>(c.f, c.claimed_ref, c.claimed_src);
+    fuse_pixel<true, false>(c.f, c.claimed_ref, c.claimed_src, nullptr);
+}
+
+// claimed_ref and claimed_src[0] null: the no-dedupe form (nothing gates `final`, the claim step is skipped)
+__global__ void __launch_bounds__(256) fuse_depth_dynamic_kernel(const FuseClaimArgs c, const FuseDynArgs d) {
+    fuse_pixel<true, true>(c.f, c.claimed_ref, c.claimed_src, &d);
 }
 
 }  // namespace itermvs
@@ -164,6 +203,18 @@ static int fill_fuse_args(FuseArgs& a, const float* depth_ref, const float* conf
     return ITERMVS_OK;
 }
 
+// the claim maps of both entry points that take them, behind fill_fuse_args
+static int fill_claim_args(FuseClaimArgs& c, const uint8_t* claimed_ref, uint8_t* const* claimed_src, int32_t S) {
+    c.claimed_ref = claimed_ref;
+    for (int s = 0; s < ITERMVS_MAX_SRC; ++s) {
+        c.claimed_src[s] = claimed_src && s < S ? claimed_src[s] : nullptr;
+        ITERMVS_RETURN_IF(claimed_src && s < S && !claimed_src[s], ITERMVS_ERR_NULL);
+        // a map that is read as claimed_ref and written as claimed_src in one launch would race with itself
+        ITERMVS_RETURN_IF(claimed_src && s < S && claimed_src[s] == claimed_ref, ITERMVS_ERR_DIMS);
+    }
+    return ITERMVS_OK;
+}
+
 extern "C" int itermvs_fuse_depth(const float* depth_ref, const float* conf_ref, const float* const* depth_src,
                                   const float* mats, int32_t S, int32_t H, int32_t W, double geo_pixel_thres,
                                   float geo_depth_thres, float photo_thres, int32_t geo_mask_thres, double* depth_avg,
@@ -186,13 +237,29 @@ extern "C" int itermvs_fuse_depth_claim(const float* depth_ref, const float* con
     const int status = fill_fuse_args(c.f, depth_ref, conf_ref, depth_src, mats, S, H, W, geo_pixel_thres, geo_depth_thres,
                                       photo_thres, geo_mask_thres, depth_avg, photo_mask, geo_mask, final_mask, geo_sum);
     if (status != ITERMVS_OK) return status;
-    c.claimed_ref = claimed_ref;
-    for (int s = 0; s < ITERMVS_MAX_SRC; ++s) {
-        c.claimed_src[s] = claimed_src && s < S ? claimed_src[s] : nullptr;
-        ITERMVS_RETURN_IF(claimed_src && s < S && !claimed_src[s], ITERMVS_ERR_NULL);
-        // a map that is read as claimed_ref and written as claimed_src in one launch would race with itself
-        ITERMVS_RETURN_IF(claimed_src && s < S && claimed_src[s] == claimed_ref, ITERMVS_ERR_DIMS);
-    }
+    const int claim_status = fill_claim_args(c, claimed_ref, claimed_src, S);
+    if (claim_status != ITERMVS_OK) return claim_status;
     hipLaunchKernelGGL(fuse_depth_claim_kernel, dim3((W + 31) / 32, (H + 7) / 8), dim3(256), 0, (hipStream_t)stream, c);
+    return itermvs_launch_status();
+}
+
+extern "C" int itermvs_fuse_depth_dynamic(const float* depth_ref, const float* conf_ref, const float* const* depth_src,
+                                          const float* mats, int32_t S, int32_t H, int32_t W, double geo_pixel_thres,
+                                          float geo_depth_thres, float photo_thres, double* depth_avg, uint8_t* photo_mask,
+                                          uint8_t* geo_mask, uint8_t* final_mask, int32_t* geo_sum, const uint8_t* claimed_ref,
+                                          uint8_t* const* claimed_src, double dyn_pixel_step, float dyn_depth_step,
+                                          int32_t n_min, int32_t n_max, uint8_t* geo_level, void* stream) {
+    FuseClaimArgs c;
+    const int status = fill_fuse_args(c.f, depth_ref, conf_ref, depth_src, mats, S, H, W, geo_pixel_thres, geo_depth_thres,
+                                      photo_thres, 0, depth_avg, photo_mask, geo_mask, final_mask, geo_sum);
+    if (status != ITERMVS_OK) return status;
+    const int claim_status = fill_claim_args(c, claimed_ref, claimed_src, S);
+    if (claim_status != ITERMVS_OK) return claim_status;
+    ITERMVS_RETURN_IF(!(isfinite(dyn_pixel_step) && dyn_pixel_step > 0.0 && isfinite(dyn_depth_step) && dyn_depth_step > 0.0f),
+                      ITERMVS_ERR_DIMS);
+    ITERMVS_RETURN_IF(n_min < 1 || n_min > n_max || n_max > ITERMVS_MAX_SRC, ITERMVS_ERR_DIMS);
+    FuseDynArgs d;
+    d.pixel_step = dyn_pixel_step; d.depth_step = dyn_depth_step; d.n_min = n_min; d.n_max = n_max; d.geo_level = geo_level;
+    hipLaunchKernelGGL(fuse_depth_dynamic_kernel, dim3((W + 31) / 32, (H + 7) / 8), dim3(256), 0, (hipStream_t)stream, c, d);
     return itermvs_launch_status();
 }

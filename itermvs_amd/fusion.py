@@ -50,16 +50,63 @@ def pair_matrices(k_ref: np.ndarray, e_ref: np.ndarray, k_src: np.ndarray, e_src
     return np.concatenate([np.asarray(p, np.float32).reshape(-1) for p in parts])
 
 
+def dynamic_problem(dyn_pixel_step, dyn_depth_step, dyn_n_min, dyn_n_max) -> Optional[str]:
+    """which part of a level rule the entry point would refuse: "steps" (the pixel step as a double and the depth step AS THE
+    FLOAT32 IT IS PASSED AS must be finite and above 0: 1e-60 rounds to 0, 1e60 to inf), "levels" (1 <= n_min <= n_max <=
+    ITERMVS_MAX_SRC) or None.  The callers word their own messages."""
+    with np.errstate(over="ignore"):
+        a, b = float(dyn_pixel_step), float(np.float32(dyn_depth_step))
+    if not (0 < a < float("inf") and 0 < b < float("inf")):
+        return "steps"
+    if not 1 <= int(dyn_n_min) <= int(dyn_n_max) <= ops.MAX_SRC:
+        return "levels"
+    return None
+
+
+def dynamic_options(consistency: str = "static", dyn_pixel_step: float = ops.DYN_PIXEL_STEP, dyn_depth_step: float = ops.DYN_DEPTH_STEP,
+                    dyn_n_min: int = ops.DYN_N_MIN, dyn_n_max: int = ops.DYN_N_MAX) -> Optional[dict]:
+    """``consistency`` "static": None (the count against ``geo_mask_thres``); "dynamic": the checked keyword arguments of the
+    level rule for ``ops.fuse_depth_dynamic`` (include/itermvs_hip.h: itermvs_fuse_depth_dynamic)"""
+    if consistency not in ("static", "dynamic"):
+        raise ValueError(f"consistency must be 'static' or 'dynamic', got {consistency!r}")
+    if consistency == "static":
+        return None
+    problem = dynamic_problem(dyn_pixel_step, dyn_depth_step, dyn_n_min, dyn_n_max)
+    if problem == "steps":
+        raise ValueError(f"dynamic consistency: dyn_pixel_step and dyn_depth_step (as float32) must be finite and above 0, got "
+                         f"{dyn_pixel_step}, {dyn_depth_step}")
+    if problem == "levels":
+        raise ValueError(f"dynamic consistency: the levels must satisfy 1 <= dyn_n_min <= dyn_n_max <= {ops.MAX_SRC}, got "
+                         f"{dyn_n_min}..{dyn_n_max}")
+    return dict(dyn_pixel_step=float(dyn_pixel_step), dyn_depth_step=float(dyn_depth_step), dyn_n_min=int(dyn_n_min),
+                dyn_n_max=int(dyn_n_max))
+
+
+def consistency_from_args(args) -> dict:
+    """the ``--geo_consistency`` / ``--dyn_*`` flags of eval.py -> the keyword arguments ``fuse_scan`` and ``filter_depth`` take"""
+    given = lambda name, default: default if getattr(args, name, None) is None else getattr(args, name)      # noqa: E731
+    levels = given("dyn_levels", (ops.DYN_N_MIN, ops.DYN_N_MAX))
+    return dict(consistency=getattr(args, "geo_consistency", "static"), dyn_pixel_step=given("dyn_pixel_step", ops.DYN_PIXEL_STEP),
+                dyn_depth_step=given("dyn_depth_step", ops.DYN_DEPTH_STEP), dyn_n_min=levels[0], dyn_n_max=levels[1])
+
+
 def fuse_reference_view(depth_ref, conf_ref, k_ref, e_ref, src_depths: Sequence, src_ks: Sequence, src_es: Sequence,
-                        geo_pixel_thres=1.0, geo_depth_thres=0.01, photo_thres=0.3, geo_mask_thres=3, device="cuda"):
+                        geo_pixel_thres=1.0, geo_depth_thres=0.01, photo_thres=0.3, geo_mask_thres=3, device="cuda",
+                        consistency="static", dyn_pixel_step=ops.DYN_PIXEL_STEP, dyn_depth_step=ops.DYN_DEPTH_STEP,
+                        dyn_n_min=ops.DYN_N_MIN, dyn_n_max=ops.DYN_N_MAX):
     """eval.py:238-269 for one reference view (numpy or torch inputs) -> torch tensors
-    (depth_est_averaged float64, photo_mask, geo_mask, final_mask uint8, geo_mask_sum int32)"""
+    (depth_est_averaged float64, photo_mask, geo_mask, final_mask uint8, geo_mask_sum int32).  ``consistency="dynamic"``: the
+    geometric mask is the level rule of ``ops.fuse_depth_dynamic`` with the four ``dyn_*`` parameters, ``geo_mask_thres`` is not
+    used and the accepting level map (uint8) is returned as a sixth tensor."""
     dev = torch.device(device)
+    dyn = dynamic_options(consistency, dyn_pixel_step, dyn_depth_step, dyn_n_min, dyn_n_max)
     as_t = lambda a: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dev, torch.float32)
     mats = np.stack([pair_matrices(np.asarray(k_ref), np.asarray(e_ref), np.asarray(k), np.asarray(e))
                      for k, e in zip(src_ks, src_es)])
-    return ops.fuse_depth(as_t(depth_ref), as_t(conf_ref), [as_t(d) for d in src_depths], torch.from_numpy(mats).to(dev),
-                          geo_pixel_thres, geo_depth_thres, photo_thres, geo_mask_thres)
+    maps = (as_t(depth_ref), as_t(conf_ref), [as_t(d) for d in src_depths], torch.from_numpy(mats).to(dev))
+    if dyn is not None:
+        return ops.fuse_depth_dynamic(*maps, None, None, geo_pixel_thres, geo_depth_thres, photo_thres, **dyn)
+    return ops.fuse_depth(*maps, geo_pixel_thres, geo_depth_thres, photo_thres, geo_mask_thres)
 
 
 def ply_header(n: int, normals: bool = False) -> bytes:
@@ -333,7 +380,9 @@ def fuse_scan(pairs: Sequence[Tuple[int, Sequence[int]]], cams, depths, confiden
               geo_pixel_thres: float, geo_depth_thres: float, photo_thres: float, geo_mask_thres: int = 3, device: str = "cuda",
               records_budget: int = 2 << 30, mask_folder: str = None, group_capacity: int = None,
               info: dict = None, dedupe: bool = False, normals: bool = False,
-              normal_edge_thres: float = 0.01, mesh=None) -> Dict[int, Tuple[float, float, float]]:
+              normal_edge_thres: float = 0.01, mesh=None, consistency: str = "static", dyn_pixel_step: float = ops.DYN_PIXEL_STEP,
+              dyn_depth_step: float = ops.DYN_DEPTH_STEP, dyn_n_min: int = ops.DYN_N_MIN,
+              dyn_n_max: int = ops.DYN_N_MAX) -> Dict[int, Tuple[float, float, float]]:
     """eval.py:215-309 for a scan that is already in memory, with the point cloud assembled on the GPU: per reference view one
     ``itermvs_fuse_depth`` and one ``itermvs_fuse_points``, enqueued back to back; the host synchronises once per GROUP of
     reference views, downloads the group's finished vertex records and appends them to the PLY.
@@ -357,9 +406,14 @@ def fuse_scan(pairs: Sequence[Tuple[int, Sequence[int]]], cams, depths, confiden
     of the mesh's budget), the emitted vertices' coordinates are kept for the default bounds, and after the last group the views are
     integrated into a volume in ``pairs`` order and marching tetrahedra writes ``mesh.path``.  The cloud, the masks and the
     returned shares are those without it.
+    consistency: "static" (default): a pixel's geometric mask is ``count >= geo_mask_thres``.  "dynamic": the level rule of
+    ``itermvs_fuse_depth_dynamic`` with ``dyn_pixel_step``, ``dyn_depth_step`` and the levels ``dyn_n_min..dyn_n_max`` takes its
+    place in one launch of that entry point per reference view, ``geo_mask_thres`` is not used; the cloud, ``dedupe``, ``normals``,
+    the mesh's kept mask, the masks of ``mask_folder`` and the returned shares all follow the dynamic ``geo``.
     -> {ref_view: (geo, photo, final mask share)} like ``filter_depth``."""
     dev = torch.device(device)
     mesh = mesh_options(mesh)
+    dyn = dynamic_options(consistency, dyn_pixel_step, dyn_depth_step, dyn_n_min, dyn_n_max)
     clock = time.perf_counter
     seconds = {"upload": 0.0, "enqueue": 0.0, "gpu_wait": 0.0, "download_wait": 0.0, "file_write": 0.0, "mask_write": 0.0}
     n_sync = n_chunks = 0
@@ -420,7 +474,10 @@ def fuse_scan(pairs: Sequence[Tuple[int, Sequence[int]]], cams, depths, confiden
                     ref, srcs = pairs[i]
                     maps = (on_dev[ref], conf[i], [on_dev[v] for v in srcs], mats[first_mat[i]:first_mat[i + 1]])
                     thres = (geo_pixel_thres, geo_depth_thres, photo_thres, geo_mask_thres)
-                    if dedupe:
+                    if dyn is not None:
+                        claims = (claimed[ref], [claimed[v] for v in srcs]) if dedupe else (None, None)
+                        avg, photo, geo, final, _, _ = ops.fuse_depth_dynamic(*maps, *claims, *thres[:3], **dyn)
+                    elif dedupe:
                         avg, photo, geo, final, _ = ops.fuse_depth_claim(*maps, claimed[ref], [claimed[v] for v in srcs], *thres)
                     else:
                         avg, photo, geo, final, _ = ops.fuse_depth(*maps, *thres)
@@ -482,7 +539,7 @@ def fuse_scan(pairs: Sequence[Tuple[int, Sequence[int]]], cams, depths, confiden
             info.update(mesh=mesh_info)
         info.update(groups=groups, synchronisations=n_sync, downloads=len(groups), download_chunks=n_chunks,
                     vertices=n_vertices, capacity=capacity, seconds=seconds, dedupe=bool(dedupe),
-                    normals=bool(normals), record_bytes=rec)
+                    normals=bool(normals), record_bytes=rec, consistency=consistency)
     return stats
 
 
@@ -490,7 +547,9 @@ def filter_depth(scan_folder: str, out_folder: str, plyfilename: str, geo_pixel_
                  photo_thres: float, images: Dict[int, np.ndarray] = None, intrinsics_scale: Tuple[float, float] = None,
                  geo_mask_thres: int = 3, device: str = "cuda", img_wh: Tuple[int, int] = None, points: str = "host",
                  save_masks: bool = False, records_budget: int = 2 << 30, info: dict = None,
-                 dedupe: bool = False, normals: bool = False, normal_edge_thres: float = 0.01, mesh=None) -> Dict[str, float]:
+                 dedupe: bool = False, normals: bool = False, normal_edge_thres: float = 0.01, mesh=None,
+                 consistency: str = "static", dyn_pixel_step: float = ops.DYN_PIXEL_STEP, dyn_depth_step: float = ops.DYN_DEPTH_STEP,
+                 dyn_n_min: int = ops.DYN_N_MIN, dyn_n_max: int = ops.DYN_N_MAX) -> Dict[str, float]:
     """eval.py:215-309: for every reference view of ``pair.txt`` fuse its depth map with its source views' and append the
     surviving pixels to one point cloud.
 
@@ -507,9 +566,13 @@ def filter_depth(scan_folder: str, out_folder: str, plyfilename: str, geo_pixel_
     ``fuse_scan``); same header, vertex order and colours, coordinates equal up to the last float64 bit of ``np.matmul``.
     ``save_masks``: also write ``<out_folder>/mask/{view:0>8}_photo.png``, ``_geo.png``, ``_final.png`` (eval.py:266-269).
     ``dedupe``: ``fuse_scan``'s, so it needs ``points="device"``.  ``normals``, ``normal_edge_thres``: ``fuse_scan``'s, with the
-    same need; ``mesh``: ``fuse_scan``'s, with the same need."""
+    same need; ``mesh``: ``fuse_scan``'s, with the same need.  ``consistency`` and the four ``dyn_*`` parameters: ``fuse_scan``'s,
+    with either value of ``points``."""
     if points not in ("host", "device"):
         raise ValueError(f"filter_depth: points must be 'host' or 'device', got {points!r}")
+    rule = dict(consistency=consistency, dyn_pixel_step=dyn_pixel_step, dyn_depth_step=dyn_depth_step, dyn_n_min=dyn_n_min,
+                dyn_n_max=dyn_n_max)
+    dynamic_options(**rule)
     if dedupe and points != "device":
         raise ValueError("filter_depth: dedupe=True needs points='device' (the claim maps live on the GPU between the reference "
                          f"views), got points={points!r}")
@@ -575,15 +638,15 @@ def filter_depth(scan_folder: str, out_folder: str, plyfilename: str, geo_pixel_
                 rgb[ref_view] = pixels.pop(ref_view) if ref_view in pixels else np.full((h, w, 3), 127, np.uint8)
         return fuse_scan(pairs, cams, depths, confs, rgb, plyfilename, geo_pixel_thres, geo_depth_thres, photo_thres,
                          geo_mask_thres, device, records_budget, mask_folder, info=info, dedupe=dedupe, normals=normals,
-                         normal_edge_thres=normal_edge_thres, mesh=mesh)
+                         normal_edge_thres=normal_edge_thres, mesh=mesh, **rule)
 
     vertexs, colors, stats = [], [], {}
     for ref_view, src_views in pairs:
         k_ref, e_ref = cam(ref_view, want_pixels=True)
         conf = confidence(ref_view)
-        avg, photo, geo, final, _ = fuse_reference_view(depth(ref_view), conf, k_ref, e_ref, [depth(v) for v in src_views],
-                                                        [cam(v)[0] for v in src_views], [cam(v)[1] for v in src_views],
-                                                        geo_pixel_thres, geo_depth_thres, photo_thres, geo_mask_thres, device)
+        avg, photo, geo, final = fuse_reference_view(depth(ref_view), conf, k_ref, e_ref, [depth(v) for v in src_views],
+                                                     [cam(v)[0] for v in src_views], [cam(v)[1] for v in src_views],
+                                                     geo_pixel_thres, geo_depth_thres, photo_thres, geo_mask_thres, device, **rule)[:4]
         final_np = final.cpu().numpy().astype(bool)
         if save_masks:
             _save_view_masks(mask_folder, ref_view, photo, geo, final)

@@ -1305,9 +1305,11 @@ CONV_FLOP_COUNTER = {"enabled": False, "flops": 0.0, "launches": 0}
 
 
 def _fuse_depth(what: str, depth_ref: Tensor, conf_ref: Tensor, depth_src: Sequence[Tensor], mats: Tensor, geo_pixel_thres: float,
-                geo_depth_thres: float, photo_thres: float, geo_mask_thres: int, claim: Optional[tuple] = None):
-    """the inputs, outputs and call that itermvs_fuse_depth and itermvs_fuse_depth_claim share; ``claim``: the two extra pointer
-    arguments of the latter"""
+                geo_depth_thres: float, photo_thres: float, geo_mask_thres: Optional[int], claim: Optional[tuple] = None,
+                dynamic: Optional[tuple] = None):
+    """the inputs, outputs and call that itermvs_fuse_depth, itermvs_fuse_depth_claim and itermvs_fuse_depth_dynamic share;
+    ``claim``: the two extra pointer arguments of the latter two; ``dynamic``: (pixel step, depth step, n_min, n_max) of the last,
+    which takes no ``geo_mask_thres`` and also returns the level map"""
     h, w = depth_ref.shape
     s = len(depth_src)
     depth_ref, conf_ref = _dev(depth_ref, "depth_ref").contiguous(), _dev(conf_ref, "conf_ref").contiguous()
@@ -1320,11 +1322,14 @@ def _fuse_depth(what: str, depth_ref: Tensor, conf_ref: Tensor, depth_src: Seque
     avg = torch.empty((h, w), device=dev, dtype=torch.float64)
     photo, geo, final = (torch.empty((h, w), device=dev, dtype=torch.uint8) for _ in range(3))
     cnt = torch.empty((h, w), device=dev, dtype=torch.int32)
+    count_thres = () if dynamic is not None else (int(geo_mask_thres),)
+    level = torch.empty((h, w), device=dev, dtype=torch.uint8) if dynamic is not None else None
+    rule = () if dynamic is None else (float(dynamic[0]), float(dynamic[1]), int(dynamic[2]), int(dynamic[3]), level.data_ptr())
     check(getattr(_lib.load(), "itermvs_" + what)(depth_ref.data_ptr(), conf_ref.data_ptr(), ptrs, mats.data_ptr(), s, h, w,
                                                   float(geo_pixel_thres), float(geo_depth_thres), float(photo_thres),
-                                                  int(geo_mask_thres), avg.data_ptr(), photo.data_ptr(), geo.data_ptr(),
-                                                  final.data_ptr(), cnt.data_ptr(), *(claim or ()), _stream()), "itermvs_" + what)
-    return avg, photo, geo, final, cnt
+                                                  *count_thres, avg.data_ptr(), photo.data_ptr(), geo.data_ptr(),
+                                                  final.data_ptr(), cnt.data_ptr(), *(claim or ()), *rule, _stream()), "itermvs_" + what)
+    return (avg, photo, geo, final, cnt) if dynamic is None else (avg, photo, geo, final, cnt, level)
 
 
 def fuse_depth(depth_ref: Tensor, conf_ref: Tensor, depth_src: Sequence[Tensor], mats: Tensor, geo_pixel_thres: float = 1.0,
@@ -1335,6 +1340,23 @@ def fuse_depth(depth_ref: Tensor, conf_ref: Tensor, depth_src: Sequence[Tensor],
                        geo_mask_thres)
 
 
+def _claim_pointers(what: str, depth_ref: Tensor, depth_src: Sequence[Tensor], claimed_ref: Optional[Tensor],
+                    claimed_src: Optional[Sequence[Tensor]]) -> tuple:
+    """the checked claim maps of ``fuse_depth_claim`` / ``fuse_depth_dynamic`` -> the two pointer arguments of their entry points"""
+    h, w = depth_ref.shape
+    maps = ([] if claimed_ref is None else [claimed_ref]) + list(claimed_src or [])
+    for t in maps:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{what}: expected CUDA/ROCm tensors - the IterMVS HIP engine has no CPU path")
+        if t.dtype != torch.uint8 or tuple(t.shape) != (h, w) or not t.is_contiguous() or t.device != depth_ref.device:
+            raise RuntimeError(f"{what}: a claim map must be a contiguous torch.uint8 tensor of shape {(h, w)} on "
+                               f"{depth_ref.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    if claimed_src is not None and len(claimed_src) != len(depth_src):
+        raise RuntimeError(f"{what}: {len(claimed_src)} claim maps for {len(depth_src)} source views")
+    ptrs = None if claimed_src is None else (C.c_void_p * len(claimed_src))(*[t.data_ptr() for t in claimed_src])
+    return (None if claimed_ref is None else claimed_ref.data_ptr(), ptrs)
+
+
 def fuse_depth_claim(depth_ref: Tensor, conf_ref: Tensor, depth_src: Sequence[Tensor], mats: Tensor,
                      claimed_ref: Optional[Tensor], claimed_src: Optional[Sequence[Tensor]], geo_pixel_thres: float = 1.0,
                      geo_depth_thres: float = 0.01, photo_thres: float = 0.3, geo_mask_thres: int = 3):
@@ -1342,19 +1364,26 @@ def fuse_depth_claim(depth_ref: Tensor, conf_ref: Tensor, depth_src: Sequence[Te
     None: nothing is marked), and whose emitting pixels mark, IN PLACE, the pixel they were verified against in each consistent
     source view's map of ``claimed_src`` (S uint8 [H,W] maps, none of them ``claimed_ref``; None: nothing is marked).  The
     contract is in include/itermvs_hip.h.  -> the tuple of ``fuse_depth``."""
-    h, w = depth_ref.shape
-    maps = ([] if claimed_ref is None else [claimed_ref]) + list(claimed_src or [])
-    for t in maps:
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise RuntimeError("fuse_depth_claim: expected CUDA/ROCm tensors - the IterMVS HIP engine has no CPU path")
-        if t.dtype != torch.uint8 or tuple(t.shape) != (h, w) or not t.is_contiguous() or t.device != depth_ref.device:
-            raise RuntimeError(f"fuse_depth_claim: a claim map must be a contiguous torch.uint8 tensor of shape {(h, w)} on "
-                               f"{depth_ref.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
-    if claimed_src is not None and len(claimed_src) != len(depth_src):
-        raise RuntimeError(f"fuse_depth_claim: {len(claimed_src)} claim maps for {len(depth_src)} source views")
-    ptrs = None if claimed_src is None else (C.c_void_p * len(claimed_src))(*[t.data_ptr() for t in claimed_src])
     return _fuse_depth("fuse_depth_claim", depth_ref, conf_ref, depth_src, mats, geo_pixel_thres, geo_depth_thres, photo_thres,
-                       geo_mask_thres, claim=(None if claimed_ref is None else claimed_ref.data_ptr(), ptrs))
+                       geo_mask_thres, claim=_claim_pointers("fuse_depth_claim", depth_ref, depth_src, claimed_ref, claimed_src))
+
+
+DYN_PIXEL_STEP, DYN_DEPTH_STEP, DYN_N_MIN, DYN_N_MAX = 0.25, 1.0 / 1300.0, 2, 10     # unverified defaults, DESIGN.md section 4c
+
+
+def fuse_depth_dynamic(depth_ref: Tensor, conf_ref: Tensor, depth_src: Sequence[Tensor], mats: Tensor,
+                       claimed_ref: Optional[Tensor] = None, claimed_src: Optional[Sequence[Tensor]] = None,
+                       geo_pixel_thres: float = 1.0, geo_depth_thres: float = 0.01, photo_thres: float = 0.3,
+                       dyn_pixel_step: float = DYN_PIXEL_STEP, dyn_depth_step: float = DYN_DEPTH_STEP,
+                       dyn_n_min: int = DYN_N_MIN, dyn_n_max: int = DYN_N_MAX):
+    """itermvs_fuse_depth_dynamic: ``fuse_depth_claim`` (claim maps optional) whose ``geo`` is the level rule of
+    include/itermvs_hip.h instead of a count against ``geo_mask_thres``: a source passes level n when its reprojection lies within
+    n * dyn_pixel_step pixels and n * dyn_depth_step (rounded to float32) of relative depth, and the pixel is accepted at the
+    smallest level n of dyn_n_min..dyn_n_max that at least n sources pass.  The average, the count and the claims stay
+    those of the base thresholds.  -> (depth_avg, photo, geo, final, count, level uint8 [H,W]: the accepting level, 0 = none)."""
+    return _fuse_depth("fuse_depth_dynamic", depth_ref, conf_ref, depth_src, mats, geo_pixel_thres, geo_depth_thres, photo_thres,
+                       None, claim=_claim_pointers("fuse_depth_dynamic", depth_ref, depth_src, claimed_ref, claimed_src),
+                       dynamic=(dyn_pixel_step, dyn_depth_step, dyn_n_min, dyn_n_max))
 
 
 POINT_RECORD_BYTES = 15      # PLY vertex of eval.py:298-308: x, y, z float32, red, green, blue uint8

@@ -250,7 +250,8 @@ def fuse_scans_from_memory(args, dataset, scans: Sequence[str], model, dev) -> D
                                            dedupe=bool(getattr(args, "fuse_dedupe", False)),
                                            normals=bool(getattr(args, "ply_normals", False)),
                                            normal_edge_thres=float(getattr(args, "normal_edge_thres", 0.01)),
-                                           mesh=fusion.mesh_options_from_args(args, os.path.join(args.outdir, scan + "_mesh.ply")))
+                                           mesh=fusion.mesh_options_from_args(args, os.path.join(args.outdir, scan + "_mesh.ply")),
+                                           **fusion.consistency_from_args(args))
             for v, (g, ph, f) in stats[scan].items():
                 print("processing {}, ref-view{:0>2}, geo_mask:{:3f} photo_mask:{:3f} final_mask: {:3f}".format(scan, v, g, ph, f))
             del store

@@ -7,7 +7,12 @@ One JSON line.  usage: fusion_bench.py [--height 1152 --width 1600 --src 10 --st
 PFMs, cameras and JPEGs in a temporary folder), then ``fusion.filter_depth`` end to end with ``points="host"`` and
 ``points="device"`` alternating, ``--repeats`` times each after one warm-up of both; wall clock around calls that end in a
 synchronise.  Per mode: seconds per scan (each repeat, median, spread) and where the time goes.  ``--trace-views N``: no
-timing, N reference views through fuse_depth + fuse_points for a kernel trace (rocprofv3 --kernel-trace --stats -- python ...)."""
+timing, N reference views through fuse_depth + fuse_points for a kernel trace (rocprofv3 --kernel-trace --stats -- python ...).
+``--dynamic``: per-view kernel time of ``itermvs_fuse_depth_dynamic`` (default steps and levels, no claim maps) against
+``itermvs_fuse_depth`` on the same inputs, ``--repeats`` blocks of ``--steps`` launches each, the two kernels alternating;
+per CALL (Python, the outputs' allocation and the launch included: enqueue-bound at small sizes) every block's mean, their median
+and spread, and the ratio of the medians.  ``--dynamic --trace-views N``: N untimed launches of each after the warm-up, for the
+kernels' own durations from ``rocprofv3 --kernel-trace --stats -- python ...`` (profiles/fuse_dynamic/README.md)."""
 import argparse
 import json
 import os
@@ -175,6 +180,46 @@ def run_trace(a):
                       "algorithmic_bytes_per_view_new_kernels": int(2 * 9 * h * w + 15 * int(counts[0, 2]))}))
 
 
+def run_dynamic(a):
+    """the dynamic leg: both kernels on one set of inputs (the noisy plane scene, so that the levels differ between pixels)"""
+    from test_fusion import _scene
+    views = _scene(a.height, a.width, a.src + 1, 0, 0.002)
+    dev = torch.device("cuda")
+    k, e, d, conf = views[0]
+    mats = torch.from_numpy(np.stack([fusion.pair_matrices(k, e, v[0], v[1]) for v in views[1:]])).to(dev)
+    dref, cref = torch.from_numpy(d).to(dev), torch.from_numpy(conf).to(dev)
+    srcs = [torch.from_numpy(v[2]).to(dev) for v in views[1:]]
+    runs = {"fuse_depth": lambda: ops.fuse_depth(dref, cref, srcs, mats), "fuse_depth_dynamic": lambda: ops.fuse_depth_dynamic(dref, cref, srcs, mats)}
+    for run in runs.values():
+        for _ in range(3):
+            run()
+    torch.cuda.synchronize()
+    level = runs["fuse_depth_dynamic"]()[5]
+    if a.trace_views:                            # nothing timed here: the kernels' own durations come from the trace around it
+        for run in runs.values():
+            for _ in range(a.trace_views):
+                run()
+        torch.cuda.synchronize()
+        print(json.dumps({"trace_views": a.trace_views, "config": {"width": a.width, "height": a.height, "src": a.src}}))
+        return
+    ms = {name: [] for name in runs}
+    for _ in range(a.repeats):
+        for name, run in runs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.steps):
+                run()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[name].append(e0.elapsed_time(e1) / a.steps)
+    med = {name: float(np.median(v)) for name, v in ms.items()}
+    print(json.dumps({"metric": "ms per call of ops.fuse_depth / ops.fuse_depth_dynamic, back to back (Python, allocation of the outputs and launch included)",
+                      "config": {"width": a.width, "height": a.height, "src": a.src, "steps": a.steps, "repeats": a.repeats},
+                      "ms_per_call": ms, "median_ms": med, "spread_ms": {n: max(v) - min(v) for n, v in ms.items()},
+                      "dynamic_over_static": med["fuse_depth_dynamic"] / med["fuse_depth"],
+                      "level_histogram": torch.bincount(level.reshape(-1).long(), minlength=11).tolist()}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scan", action="store_true", help="time filter_depth end to end, points='host' against points='device'")
@@ -187,9 +232,12 @@ def main():
     ap.add_argument("--src", type=int, default=10)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dynamic", action="store_true", help="time itermvs_fuse_depth_dynamic against itermvs_fuse_depth")
     a = ap.parse_args()
     if a.scan:
         return run_scan(a)
+    if a.dynamic:
+        return run_dynamic(a)
     if a.trace_views:
         return run_trace(a)
     from test_fusion import _scene
