@@ -151,6 +151,25 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--mesh_budget_gb", type=float, default=16.0,
                    help="--mesh: GPU memory in GiB that the kept fused views (9 bytes per pixel and view), the volume, the extraction "
                         "workspace and the mesh buffers may take together; a larger request stops with the bytes it needs.  A choice")
+    p.add_argument("--clean_cloud", default=None, choices=["statistical", "radius"],
+                   help="--filter: also write <outdir>/<scan>_clean.ply, the scan's cloud without its outliers (floaters: sky pixels, "
+                        "specular surfaces, thin structures that pass the masks in a few views); <scan>.ply and every other output "
+                        "stay byte for byte as without the flag, the kept vertex records are copied unchanged and in order.  "
+                        "statistical: a vertex goes when the mean distance to its --clean_k nearest neighbours exceeds the cloud's "
+                        "mean of that distance by --clean_std_ratio standard deviations, or fewer than k vertices lie within "
+                        "--clean_max_dist (Open3D's remove_statistical_outlier; itermvs_cloud_knn_mean).  radius: a vertex goes when "
+                        "fewer than --clean_min_neighbours others lie within --clean_radius (itermvs_cloud_radius_count)")
+    p.add_argument("--clean_k", type=int, default=None, help="--clean_cloud statistical: neighbours per vertex, 1 .. 32 (default 20, "
+                                                              "Open3D's usual value; not a measured optimum)")
+    p.add_argument("--clean_std_ratio", type=float, default=None,
+                   help="--clean_cloud statistical: standard deviations above the mean (default 2.0, Open3D's usual value; not a "
+                        "measured optimum)")
+    p.add_argument("--clean_max_dist", type=float, default=None,
+                   help="--clean_cloud statistical: how far the neighbour search looks, in world units (default: 0.02 x the diagonal "
+                        "of the cloud's 1 %% .. 99 %% quantile box; a choice, not a measured optimum)")
+    p.add_argument("--clean_radius", type=float, default=None, help="--clean_cloud radius: the radius in world units (no default)")
+    p.add_argument("--clean_min_neighbours", type=int, default=None,
+                   help="--clean_cloud radius: other vertices a vertex needs within the radius (default 2)")
     p.add_argument("--no_pfm", action="store_true",
                    help="--fuse_source memory only: do not write the depth / confidence PFMs, only the PLY (and the masks of "
                         "--save_masks) reaches the disk")
@@ -329,6 +348,45 @@ def check_geo_consistency(args) -> str:
     return mode
 
 
+CLEAN_OPTIONS = ("clean_k", "clean_std_ratio", "clean_max_dist", "clean_radius", "clean_min_neighbours")
+
+
+def check_clean_cloud(args):
+    """--clean_cloud needs --filter, radius needs --clean_radius, and a --clean_* option needs --clean_cloud: argparse errors
+    (usage, exit status 2) before any work.  -> the method or None"""
+    from itermvs_amd import cloud_filter
+    method = getattr(args, "clean_cloud", None)
+    error = build_parser().error
+    given = [o for o in CLEAN_OPTIONS if getattr(args, o, None) is not None]
+    if method is None:
+        if given:
+            error("--{} needs --clean_cloud".format(given[0]))
+        return None
+    if not args.filter:
+        error("--clean_cloud needs --filter (it cleans the fused cloud of each scan)")
+    if method == "radius" and getattr(args, "clean_radius", None) is None:
+        error("--clean_cloud radius needs --clean_radius (world units; there is no default)")
+    problem = cloud_filter.method_problem(method, *[getattr(args, o, None) for o in CLEAN_OPTIONS])
+    if problem:
+        error("--clean_cloud {}: --clean_{}".format(method, problem))
+    return method
+
+
+def clean_scan_cloud(args, scan: str, device) -> None:
+    """--clean_cloud: <outdir>/<scan>.ply -> <outdir>/<scan>_clean.ply (itermvs_amd.cloud_filter); the cloud itself is only read"""
+    from itermvs_amd import cloud_filter
+    method = getattr(args, "clean_cloud", None)
+    if method is None or not os.path.isfile(os.path.join(args.outdir, scan + ".ply")):
+        return
+    info = {}
+    fn = cloud_filter.mask_function(method, *[getattr(args, o, None) for o in CLEAN_OPTIONS], device=device, info=info)
+    got = cloud_filter.clean_ply(os.path.join(args.outdir, scan + ".ply"), os.path.join(args.outdir, scan + "_clean.ply"), fn)
+    print("cleaning {} ({}): kept {} removed {} of {} vertices{}, sort {:.3f} s search {:.3f} s".format(
+        scan, method, got["kept"], got["removed"], got["vertices"],
+        ", isolated {} threshold {:.6g}".format(info.get("isolated", 0), info.get("threshold", float("nan")))
+        if method == "statistical" else "", info.get("seconds_sort", 0.0), info.get("seconds_search", 0.0)))
+
+
 def fuse_memory(args) -> dict:
     """--fuse_source memory: depth maps and point clouds in one pass (itermvs_amd.scan_fuse); scans are sharded over the
     ranks whole, like ``fuse_scans`` shards them.  -> {scan: {ref_view: (geo, photo, final mask share)}} of this rank"""
@@ -338,6 +396,7 @@ def fuse_memory(args) -> dict:
     check_ply_normals(args)
     check_mesh(args)
     check_geo_consistency(args)
+    check_clean_cloud(args)
     check_feature_cache(args)
     rank, local_rank, world = shard.init_distributed()
     torch.cuda.set_device(local_rank)
@@ -345,7 +404,10 @@ def fuse_memory(args) -> dict:
     dataset = make_dataset(args)
     model = load_model(args, dev)
     scans = list(dict.fromkeys(m[0] for m in dataset.metas))
-    stats = fuse_scans_from_memory(args, dataset, [scans[i] for i in shard.shard_indices(len(scans), rank, world)], model, dev)
+    mine = [scans[i] for i in shard.shard_indices(len(scans), rank, world)]
+    stats = fuse_scans_from_memory(args, dataset, mine, model, dev)
+    for scan in mine:
+        clean_scan_cloud(args, scan, dev)
     shard.barrier()
     return stats
 
@@ -447,6 +509,7 @@ def fuse_scans(args) -> int:
     normals = check_ply_normals(args)
     check_mesh(args)
     check_geo_consistency(args)
+    check_clean_cloud(args)
     rank, local_rank, world = shard.init_distributed()
     dev = "cuda:%d" % local_rank
     scans = sorted(d for d in os.listdir(args.testpath)
@@ -464,6 +527,7 @@ def fuse_scans(args) -> int:
                                     **fusion.consistency_from_args(args))
         for v, (g, ph, f) in stats.items():
             print("processing {}, ref-view{:0>2}, geo_mask:{:3f} photo_mask:{:3f} final_mask: {:3f}".format(scan, v, g, ph, f))
+        clean_scan_cloud(args, scan, dev)
         n += 1
     shard.barrier()
     return n
@@ -476,6 +540,7 @@ if __name__ == "__main__":
     check_ply_normals(a)
     check_mesh(a)
     check_geo_consistency(a)
+    check_clean_cloud(a)
     if check_fuse_source(a) == "memory":
         fuse_memory(a)
     else:

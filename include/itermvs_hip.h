@@ -1003,6 +1003,41 @@ int itermvs_cloud_umeyama_sums(const float* q, int64_t n, const double* T, const
                                const float* target, int64_t nt, double* partials, double* sums, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Outlier removal of a fused cloud (csrc/cloud_filter.hip; host side: itermvs_amd/cloud_filter.py).  Additions compatible with
+ * ABI 20.  The queries are the targets: xyz_sorted float32 [n][3] / keys_sorted int64 [n] are ONE cloud in key order on the given
+ * grid (itermvs_cloud_cell_keys, sorted by the caller), perm int64 [n] the sorted position's index in the caller's unsorted cloud;
+ * outputs are written at perm[position], that is in the caller's order (a perm value outside [0, n) writes nothing).  One lane per
+ * sorted position.  Arithmetic: fp64 on the float32 coordinates, d2 = ((dx*dx) + (dy*dy)) + (dz*dz) without contraction.  A query
+ * skips its own sorted position and nothing else: another point at distance 0 is a neighbour.  A point with key INT64_MAX (a
+ * non-finite coordinate, or outside the grid) is nobody's neighbour and, as a query, gets flag 1 / count 0.  Checks before any
+ * launch: ITERMVS_ERR_NULL for a NULL pointer (index excepted), ITERMVS_ERR_DIMS for the grid errors of the searches above and
+ * what each entry adds.  No atomics, no LDS, nothing allocates or synchronises; one launch each.
+ *
+ * itermvs_cloud_knn_mean -- the mean distance to the k nearest other points (Open3D remove_statistical_outlier, PCL
+ *   StatisticalOutlierRemoval), limited to `cap`.  Queries: every sorted position or, with index != NULL, the n_index sorted
+ *   positions of index (int64; entries outside [0, n) are skipped).  The call walks the rings 0 .. rings - 1 of cells around the
+ *   query's cell (csrc/cloud_grid.hpp) keeping the k smallest d2, ascending d2_1 <= ... <= d2_k (+Inf until found), and stops
+ *   before ring r >= 1 as soon as d2_k <= lb * lb or lb >= cap, lb = (r - 1) * edge * (1 - 2^-20).  Stopped that way:
+ *     isolated <=> !(d2_k <= cap * cap)  (the product rounded once): fewer than k other points within cap.  flag 1, mean +Inf.
+ *     otherwise flag 0, mean = (((0.0 + sqrt(d2_1)) + sqrt(d2_2)) + ... + sqrt(d2_k)) / k, IEEE sqrt, added in ascending order.
+ *   Rings used up first: flag 2, mean +Inf -- the caller repeats the query on a coarser grid from the start; no state is carried.
+ *   Flags 0 and 1 and the mean do not depend on the grid.  mean fp64 [n], flag uint8 [n].
+ *   ITERMVS_ERR_DIMS also for k outside 1 .. 32, n <= k, cap not finite or <= 0, rings outside 1 .. 2^21, n_index outside 1 .. n.
+ *
+ * itermvs_cloud_radius_count -- PCL RadiusOutlierRemoval's count.  count[perm[i]] (int32) = min(number of other points with
+ *   d2 <= r * r (the product rounded once, inclusive), limit).  The walk's cap is r: it ends when the ring bound reaches r, or one
+ *   ring after `limit` neighbours are counted.  ITERMVS_ERR_DIMS also for r not finite or <= 0, limit < 1, and a grid whose
+ *   edge needs more than 64 rings to reach r ((r_ring - 1) * edge * (1 - 2^-20) >= r first at r_ring > 64).
+ * ------------------------------------------------------------------------------------------ */
+int itermvs_cloud_knn_mean(const float* xyz_sorted, const int64_t* keys_sorted, const int64_t* perm, int64_t n,
+                           const int64_t* index, int64_t n_index, double ox, double oy, double oz, int32_t nx, int32_t ny,
+                           int32_t nz, double edge, int32_t k, double cap, int32_t rings, double* mean, uint8_t* flag,
+                           void* stream);
+int itermvs_cloud_radius_count(const float* xyz_sorted, const int64_t* keys_sorted, const int64_t* perm, int64_t n, double ox,
+                               double oy, double oz, int32_t nx, int32_t ny, int32_t nz, double edge, double r, int32_t limit,
+                               int32_t* count, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * itermvs_image_pyramid --the input side of the path: datasets/dtu_yao_eval.py:61-74
  * (read_img) on the GPU.  src [V,Hs,Ws,3] uint8 interleaved RGB (the decoded images of one sample, same size) ->
  *   level0 [V,3,H,W]       = cv2.resize(2 * src / 255. - 1, (W, H), INTER_LINEAR)   (float32)

@@ -241,6 +241,10 @@ PROTOTYPES = {
     "itermvs_cloud_umeyama_groups": (C.c_int, [C.c_int64]),
     "itermvs_cloud_umeyama_sums": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "itermvs_cloud_knn_mean": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_int64] + [C.c_double] * 3 + [C.c_int32] * 3 +
+                               [C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "itermvs_cloud_radius_count": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_double] * 3 + [C.c_int32] * 3 +
+                                   [C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]),
     "itermvs_profile_graph_count": (C.c_int, []),
     "itermvs_profile_graph_read": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "itermvs_profile_collect": (C.c_int, [C.POINTER(C.c_int32), c_float_p, C.c_int32]),

@@ -1761,6 +1761,36 @@ def cloud_umeyama_sums(q: Tensor, T, idx: Tensor, d2: Tensor, target: Tensor) ->
     return sums
 
 
+def cloud_knn_mean(xyz_sorted: Tensor, keys_sorted: Tensor, perm: Tensor, grid: CloudGrid, k: int, cap: float, rings: int,
+                   mean: Tensor, flag: Tensor, index: Optional[Tensor] = None) -> None:
+    """itermvs_cloud_knn_mean: one grid's rings of the k-nearest search of a key-sorted cloud against itself.  mean float64 [n] and
+    flag uint8 [n] are written in the caller's order (at perm[position]) for every sorted position, or for the positions of
+    ``index`` (int64): flag 0 = settled (mean = the mean distance to the k nearest other points), 1 = isolated (fewer than k within
+    ``cap``; mean +Inf), 2 = rings used up (mean +Inf; repeat on a coarser grid).  Nothing is read back."""
+    n = _cloud("cloud_knn_mean", xyz_sorted, "xyz_sorted").shape[0]
+    for t, dt, name in ((keys_sorted, torch.int64, "keys_sorted"), (perm, torch.int64, "perm"), (mean, torch.float64, "mean"),
+                        (flag, torch.uint8, "flag")):
+        if _cloud("cloud_knn_mean", t, name, dt, ()).numel() != n:
+            raise RuntimeError(f"cloud_knn_mean: {name} must have {n} elements, got {t.numel()}")
+    if index is not None:
+        _cloud("cloud_knn_mean", index, "index", torch.int64, ())
+    check(_lib.load().itermvs_cloud_knn_mean(_ptr(xyz_sorted), _ptr(keys_sorted), _ptr(perm), n, _ptr(index),
+                                             0 if index is None else index.numel(), *grid.args(), int(k), float(cap), int(rings),
+                                             _ptr(mean), _ptr(flag), _stream()), "itermvs_cloud_knn_mean")
+
+
+def cloud_radius_count(xyz_sorted: Tensor, keys_sorted: Tensor, perm: Tensor, grid: CloudGrid, radius: float, limit: int,
+                       count: Tensor) -> None:
+    """itermvs_cloud_radius_count: count int32 [n], in the caller's order (at perm[position]) = min(number of other points with
+    d2 <= radius * radius, limit) for every point of a key-sorted cloud.  Nothing is read back."""
+    n = _cloud("cloud_radius_count", xyz_sorted, "xyz_sorted").shape[0]
+    for t, dt, name in ((keys_sorted, torch.int64, "keys_sorted"), (perm, torch.int64, "perm"), (count, torch.int32, "count")):
+        if _cloud("cloud_radius_count", t, name, dt, ()).numel() != n:
+            raise RuntimeError(f"cloud_radius_count: {name} must have {n} elements, got {t.numel()}")
+    check(_lib.load().itermvs_cloud_radius_count(_ptr(xyz_sorted), _ptr(keys_sorted), _ptr(perm), n, *grid.args(), float(radius),
+                                                 int(limit), _ptr(count), _stream()), "itermvs_cloud_radius_count")
+
+
 CORRNET_WEIGHT_FLOATS = 14288
 CORRNET_WEIGHT_FLOATS_SPLIT3 = 23120     # bf16x3 form: conv0 + conv2 + the two transposed convolutions as split bf16 operands
 
