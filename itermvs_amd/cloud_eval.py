@@ -4,8 +4,8 @@ the reduced prediction to the ground truth inside the observability mask, comple
 the table plane to the reduced prediction, both in mm, outliers beyond 20 mm discarded.
 
 All arithmetic is fp64 on the float32 coordinates of the PLY files, the squared distance ((dx*dx) + (dy*dy)) + (dz*dz), the
-distance its IEEE sqrt.  Sorting by cell key, compaction and the statistics are torch; the fixed-radius search, the ring
-search and the mask lookup are HIP.  Differences from the MATLAB scripts: the visiting order of the
+distance its IEEE sqrt.  Sorting by cell key (``cloud_grid.sort_into_cells``), compaction and the statistics are torch; the
+fixed-radius search, the ring search and the mask lookup are HIP.  Differences from the MATLAB scripts: the visiting order of the
 reduction is an explicit input (``randperm`` is not reproducible); a distance is capped at ``cap`` where MATLAB returns the
 distance to the nearest point of the block enlarged by ``cap`` (every consumer discards >= 20); the one-ulp seams between
 neighbouring blocks are not reproduced; non-finite points are never kept."""
@@ -20,23 +20,12 @@ import numpy as np
 import torch
 
 from . import ops
-from .ops import CloudGrid
+from .cloud_grid import points, sort_into_cells, two_grid_plan
 
 Tensor = torch.Tensor
 
-MAX_CELL_DIM = 1 << 21                     # csrc/cloud_eval.hip: kMaxCellDim
-RING_SHRINK = 1.0 - 2.0 ** -20             # csrc/cloud_eval.hip: kRingShrink
 EDGE_SLACK = 1.0 + 2.0 ** -20              # the reduction's cells are this much wider than dst: the 27 cells hold the radius
-FINE_RINGS = 4                             # rings of the fine grid before the rest of the search moves to the coarse one
 USED_SETS = (1, 4, 9, 10, 11, 12, 13, 15, 23, 24, 29, 32, 33, 34, 48, 49, 62, 75, 77, 110, 114, 118)     # BaseEvalMain_web.m:24
-
-
-def _points(what: str, pts: Tensor) -> Tensor:
-    if not isinstance(pts, torch.Tensor) or not pts.is_cuda:
-        raise RuntimeError(f"{what}: expected a CUDA/ROCm tensor - the IterMVS HIP engine has no CPU path")
-    if pts.dtype != torch.float32 or pts.dim() != 2 or pts.shape[1] != 3:
-        raise RuntimeError(f"{what}: points must be float32 [n,3], got {pts.dtype} {tuple(pts.shape)}")
-    return pts.contiguous()
 
 
 def _bb(bb) -> np.ndarray:
@@ -44,23 +33,6 @@ def _bb(bb) -> np.ndarray:
     if b.shape != (2, 3) or not np.isfinite(b).all():
         raise ValueError(f"bb must be a finite [2,3] array (BB of ObsMask<N>_10.mat), got shape {b.shape}")
     return b
-
-
-def grid_for(pts: Tensor, edge: float, what: str) -> CloudGrid:
-    """the grid of cells of edge ``edge`` over the extent of finite float32 [n,3] points (one synchronisation: the extent comes
-    to the host); an extent of more than 2^21 cells on an axis raises"""
-    lo, hi = pts.min(0).values.double().cpu(), pts.max(0).values.double().cpu()
-    dims = [int(math.floor((float(hi[a]) - float(lo[a])) / edge)) + 1 for a in range(3)]
-    if max(dims) > MAX_CELL_DIM:
-        raise ValueError(f"{what}: the cloud spans {dims} cells of edge {edge}; at most {MAX_CELL_DIM} per axis fit the cell key "
-                         "(remove the far outliers, or evaluate in the dataset's units)")
-    return CloudGrid(tuple(float(v) for v in lo), tuple(dims), float(edge))
-
-
-def _sort_by_cell(pts: Tensor, grid: CloudGrid) -> Tuple[Tensor, Tensor, Tensor]:
-    keys = ops.cloud_cell_keys(pts, grid)
-    keys, perm = torch.sort(keys)
-    return pts[perm].contiguous(), keys, perm
 
 
 def inverse_permutation(order: Tensor, n: int) -> Tensor:
@@ -90,7 +62,7 @@ def reduce_points(pts: Tensor, dst: float = 0.2, order: Optional[Tensor] = None,
     other point with d2 <= dst*dst.  For a given order the mask equals the sequential loop's exactly; it is computed by rounds
     of ``itermvs_cloud_reduce_round`` (``rounds_per_sync`` launches per read-back of the undecided count).  Non-finite points
     are never kept and remove nobody.  ``info`` receives rounds, non_finite, kept, and the seconds of sort and rounds."""
-    pts = _points("reduce_points", pts)
+    pts = points("reduce_points", pts)
     n = pts.shape[0]
     if not (dst > 0 and math.isfinite(dst)):
         raise ValueError(f"reduce_points: dst must be positive, got {dst}")
@@ -99,15 +71,11 @@ def reduce_points(pts: Tensor, dst: float = 0.2, order: Optional[Tensor] = None,
     order = default_order(n, seed) if order is None else order
     rank = inverse_permutation(order.to(dev), n)
     t0 = time.perf_counter()
-    finite = torch.isfinite(pts).all(1)
-    idx = torch.nonzero(finite).squeeze(1)
-    m = int(idx.numel())
+    sc = sort_into_cells(pts, dst * EDGE_SLACK, "reduce_points")
+    m = int(sc.perm.numel())
     stats = {"rounds": 0, "non_finite": n - m, "kept": 0, "seconds_sort": 0.0, "seconds_rounds": 0.0}
     if m:
-        p = pts[idx]
-        grid = grid_for(p, dst * EDGE_SLACK, "reduce_points")
-        xyz, keys, perm = _sort_by_cell(p, grid)
-        rank_sorted = rank[idx][perm].contiguous()
+        rank_sorted = rank[sc.perm].contiguous()
         state = torch.zeros((m,), device=dev, dtype=torch.int32)
         torch.cuda.synchronize(dev)
         t1 = time.perf_counter()
@@ -116,7 +84,7 @@ def reduce_points(pts: Tensor, dst: float = 0.2, order: Optional[Tensor] = None,
         while True:                                   # bounded: every round decides at least the earliest undecided point
             counts = torch.zeros((per,), device=dev, dtype=torch.int32)
             for r in range(per):
-                ops.cloud_reduce_round(xyz, keys, rank_sorted, grid, dst, state, counts[r:r + 1])
+                ops.cloud_reduce_round(sc.xyz, sc.keys, rank_sorted, sc.grid, dst, state, counts[r:r + 1])
             left = counts.cpu().tolist()
             done_at = next((r for r, c in enumerate(left) if c == 0), None)
             stats["rounds"] += per if done_at is None else done_at + 1
@@ -125,7 +93,7 @@ def reduce_points(pts: Tensor, dst: float = 0.2, order: Optional[Tensor] = None,
             if stats["rounds"] > m + per:
                 raise RuntimeError("reduce_points: the rounds did not converge (state corrupted?)")
         stats["seconds_rounds"] = time.perf_counter() - t1
-        keep[idx[perm]] = state == 1
+        keep[sc.perm] = state == 1
         stats["kept"] = int(keep.sum())
     if info is not None:
         info.update(stats)
@@ -143,21 +111,13 @@ def covered_region(bb, cap: float) -> Tuple[np.ndarray, np.ndarray]:
     return lo, hi
 
 
-def max_ring(cap: float, edge: float) -> int:
-    """the first ring r whose lower bound (r - 1) * edge * RING_SHRINK reaches ``cap``: rings 0 .. r - 1 finish every search"""
-    r = int(math.ceil(cap / (edge * RING_SHRINK))) + 1
-    while (r - 1) * edge * RING_SHRINK < cap:
-        r += 1
-    return r
-
-
 def capped_nn_distance(q_from: Tensor, q_to: Tensor, bb, cap: float = 60.0, cell: float = 1.0, info: Optional[dict] = None) -> Tensor:
     """MaxDistCP.m (Qto, Qfrom, BB, MaxDist): float64 [n_from] = min(distance to the nearest ``q_to`` point, cap) for every
     ``q_from`` point inside the region the script's blocks cover; ``cap`` for every other point and when no target lies within
-    ``cap``.  Targets are sorted into a grid of ``cell``-wide cells (searched ``FINE_RINGS`` rings far) and, for the queries
-    that does not settle, into one of cap / 8; targets farther than ``cap`` from the region cannot matter and are dropped, like
+    ``cap``.  Targets are sorted into a grid of ``cell``-wide cells and, for the queries that do not settle there, into a
+    coarser one (``cloud_grid.two_grid_plan``); targets farther than ``cap`` from the region cannot matter and are dropped, like
     the script's enlarged blocks do."""
-    q_from, q_to = _points("capped_nn_distance", q_from), _points("capped_nn_distance", q_to)
+    q_from, q_to = points("capped_nn_distance", q_from), points("capped_nn_distance", q_to)
     if not (cap > 0 and cell > 0 and math.isfinite(cap) and math.isfinite(cell)):
         raise ValueError(f"capped_nn_distance: cap and cell must be positive, got {cap}, {cell}")
     lo, hi = covered_region(bb, cap)
@@ -175,21 +135,19 @@ def capped_nn_distance(q_from: Tensor, q_to: Tensor, bb, cap: float = 60.0, cell
         best = torch.full((nq,), float("inf"), device=dev, dtype=torch.float64)
         done = torch.zeros((nq,), device=dev, dtype=torch.uint8)
         region = list(lo) + list(hi)
-        full = max_ring(cap, cell)
-        grid = grid_for(t, cell, "capped_nn_distance")
-        ts, keys, _ = _sort_by_cell(t, grid)
+        plan = two_grid_plan(cap, cell)
+        fine = sort_into_cells(t, cell, "capped_nn_distance", extent=t)              # t is finite: nothing is dropped or keyless
         torch.cuda.synchronize(dev)
         t1 = time.perf_counter()
         stats["seconds_sort"] = t1 - t0
-        ops.cloud_nn_distance(q_from, ts, keys, grid, region, cap, min(full, FINE_RINGS), best, done, dist)
-        if full > FINE_RINGS:
+        ops.cloud_nn_distance(q_from, fine.xyz, fine.keys, fine.grid, region, cap, plan.fine_rings, best, done, dist)
+        if plan.coarse_edge is not None:
             todo = torch.nonzero(done == 0).squeeze(1)
             stats["second_pass"] = int(todo.numel())
-            if todo.numel():
-                coarse = max(cap / 8.0, cell)
-                grid2 = grid_for(t, coarse, "capped_nn_distance")
-                ts2, keys2, _ = _sort_by_cell(t, grid2)
-                ops.cloud_nn_distance(q_from, ts2, keys2, grid2, region, cap, max_ring(cap, coarse), best, done, dist, index=todo)
+            if todo.numel():                           # best / done carry the search over; the second sort counts as search time
+                coarse = sort_into_cells(t, plan.coarse_edge, "capped_nn_distance", extent=t)
+                ops.cloud_nn_distance(q_from, coarse.xyz, coarse.keys, coarse.grid, region, cap, plan.coarse_rings, best, done, dist,
+                                      index=todo)
         torch.cuda.synchronize(dev)
         stats["seconds_search"] = time.perf_counter() - t1
     if info is not None:
@@ -200,7 +158,7 @@ def capped_nn_distance(q_from: Tensor, q_to: Tensor, bb, cap: float = 60.0, cell
 def points_in_mask(pts: Tensor, obs_mask: Tensor, bb, res: float) -> Tensor:
     """PointCompareMain.m:32-41: bool [n] = the point's voxel round(((p - bb[0]) / res) + 1) (MATLAB's round: half away from
     zero) lies inside ``obs_mask`` (uint8 [sx,sy,sz], indexed [x-1, y-1, z-1]) and is set"""
-    pts = _points("points_in_mask", pts)
+    pts = points("points_in_mask", pts)
     b = _bb(bb)
     if not isinstance(obs_mask, torch.Tensor) or obs_mask.dim() != 3:
         raise RuntimeError("points_in_mask: obs_mask must be a [sx,sy,sz] tensor")
@@ -224,8 +182,8 @@ def compare_points(pred: Tensor, gt: Tensor, obs_mask: Tensor, bb, res: float, p
     size, the downsample factor (reducePts_haa.m:35) and the seconds per stage."""
     red, nn1, nn2 = {}, {}, {}
     keep = reduce_points(pred, dst, order, seed, info=red)
-    qdata = _points("compare_points", pred)[keep].contiguous()
-    gt = _points("compare_points", gt)
+    qdata = points("compare_points", pred)[keep].contiguous()
+    gt = points("compare_points", gt)
     ddata = capped_nn_distance(qdata, gt, bb, cap, cell, info=nn1)               # MaxDistCP(Qstl, Qdata, BB, MaxDist)
     dstl = capped_nn_distance(gt, qdata, bb, cap, cell, info=nn2)                # MaxDistCP(Qdata, Qstl, BB, MaxDist)
     t0 = time.perf_counter()

@@ -2,7 +2,7 @@
 ``remove_statistical_outlier`` / PCL's ``StatisticalOutlierRemoval`` and the count rule of PCL's ``RadiusOutlierRemoval``, plus
 the file side that applies a mask to a PLY without touching the kept records.
 
-The searches run over the sorted uniform grid of ``cloud_eval`` (``grid_for``, ``_sort_by_cell``) with the cloud as its own
+The searches run over the sorted uniform grid of ``cloud_grid`` (``sort_into_cells``, ``two_grid_plan``) with the cloud as its own
 target set: all arithmetic is fp64 on the float32 coordinates, the squared distance ((dx*dx) + (dy*dy)) + (dz*dz), the distance
 its IEEE sqrt.  A point is never its own neighbour; another point at the same place is.  A point with a non-finite coordinate is
 nobody's neighbour and is itself isolated (statistical) or has count 0 (radius): it is always removed.
@@ -21,13 +21,11 @@ import numpy as np
 import torch
 
 from . import ops
-from .cloud_eval import MAX_CELL_DIM, _points, _sort_by_cell, grid_for, max_ring
+from .cloud_grid import finite_extent, floor_edge, grid_for, points, sort_into_cells, two_grid_plan
 from .data_io import _PLY_TYPES
 
 Tensor = torch.Tensor
 
-FINE_RINGS = 4                             # rings of the fine grid before the unsettled queries restart on the coarse one
-COARSE_SHARE = 8.0                         # coarse edge = cap / 8 (or the fine edge if that is larger)
 MAX_K = 32                                 # csrc/cloud_filter.hip: kKnnMaxK
 CAP_SHARE = 0.02                           # default cap = this share of the quantile box's diagonal
 CAP_QUANTILE = 0.01                        # ... the box of fusion.mesh_bounds(xyz, 0.01)
@@ -45,18 +43,6 @@ def threshold_bound(n: int, t: float) -> float:
     return 2.0 * (n + 8) * 2.0 ** -53 * abs(t)
 
 
-def _extent(pts: Tensor, finite: Tensor) -> Tuple[Tensor, float]:
-    """the finite points (the cloud itself when all are) and the longest side of their bounding box"""
-    p = pts if bool(finite.all()) else pts[finite]
-    side = float((p.max(0).values.double() - p.min(0).values.double()).max()) if p.shape[0] else 0.0
-    return p, side
-
-
-def _floor_edge(edge: float, side: float) -> float:
-    """``edge``, or the smallest edge whose grid over a box of longest side ``side`` still fits the cell key"""
-    return max(float(edge), side / float(MAX_CELL_DIM // 2))
-
-
 def default_edge(pts: Tensor, k: int, cap: float) -> float:
     """the cell edge ``knn_mean_distance`` uses when none is given: the edge at which an occupied cell holds about ``k`` points.
     The occupancy o = finite points / occupied cells is measured on a trial grid of edge e0 = longest side of the 1 % .. 99 %
@@ -64,23 +50,15 @@ def default_edge(pts: Tensor, k: int, cap: float) -> float:
     edge = e0 * sqrt(k / o), held inside [what the cell key allows, cap].  Rings 0 and 1 then hold about 9 k points of a
     surface and the k-th neighbour lies about 0.56 edge away: most queries stop before ring 2."""
     from .fusion import mesh_bounds
-    finite = torch.isfinite(pts).all(1)
-    p, side = _extent(pts, finite)
+    p, side = finite_extent(pts)
     if p.shape[0] == 0 or side == 0.0:
         return float(cap)
     b = mesh_bounds(p, CAP_QUANTILE)
     e0 = max(b[3 + a] - b[a] for a in range(3)) / TRIAL_CELLS
-    e0 = _floor_edge(e0 if e0 > 0.0 else side / TRIAL_CELLS, side)
+    e0 = floor_edge(e0 if e0 > 0.0 else side / TRIAL_CELLS, side)
     keys = ops.cloud_cell_keys(p, grid_for(p, e0, "knn_mean_distance"))
     occupancy = p.shape[0] / max(int(torch.unique(keys).numel()), 1)
-    return _floor_edge(min(e0 * math.sqrt(k / occupancy), float(cap)), side)
-
-
-def _sorted_cloud(pts: Tensor, p: Tensor, edge: float, what: str):
-    """``pts`` (all points; the non-finite ones get no key and sort last) in key order on the grid of edge ``edge`` over ``p``"""
-    grid = grid_for(p, edge, what)
-    xyz, keys, perm = _sort_by_cell(pts, grid)
-    return grid, xyz, keys, perm
+    return floor_edge(min(e0 * math.sqrt(k / occupancy), float(cap)), side)
 
 
 def knn_mean_distance(xyz: Tensor, k: int, cap: float, edge: Optional[float] = None, info: Optional[dict] = None) -> Tuple[Tensor, Tensor]:
@@ -88,10 +66,10 @@ def knn_mean_distance(xyz: Tensor, k: int, cap: float, edge: Optional[float] = N
     fewer than k OTHER points lie at d2 <= cap * cap; otherwise m is the mean distance to its k nearest other points, the
     square roots added in ascending order in fp64 (m is +Inf for an isolated point).  Two grids like ``capped_nn_distance``: the
     cloud is sorted into cells of ``edge`` (default: ``default_edge``) and searched ``FINE_RINGS`` rings far; the queries whose
-    rings run out restart, with no state carried over, on a grid of cap / 8 whose rings reach ``cap``.  The result does not
-    depend on ``edge``.  ``info`` receives edge, coarse_edge, second_pass (queries), isolated, non_finite, seconds_sort,
-    seconds_search."""
-    pts = _points("knn_mean_distance", xyz)
+    rings run out restart, with no state carried over, on the coarse grid of ``cloud_grid.two_grid_plan``, whose rings reach
+    ``cap``.  The result does not depend on ``edge``.  ``info`` receives edge, coarse_edge, second_pass (queries), isolated,
+    non_finite, seconds_sort, seconds_search."""
+    pts = points("knn_mean_distance", xyz)
     n, dev = pts.shape[0], pts.device
     k = int(k)
     if not 1 <= k <= MAX_K:
@@ -105,32 +83,31 @@ def knn_mean_distance(xyz: Tensor, k: int, cap: float, edge: Optional[float] = N
     t0 = time.perf_counter()
     mean = torch.full((n,), float("inf"), device=dev, dtype=torch.float64)
     flag = torch.full((n,), ISOLATED, device=dev, dtype=torch.uint8)
-    finite = torch.isfinite(pts).all(1)
-    p, side = _extent(pts, finite)
+    p, side = finite_extent(pts)
     stats = {"edge": None, "coarse_edge": None, "second_pass": 0, "isolated": n, "non_finite": n - int(p.shape[0]),
              "seconds_sort": 0.0, "seconds_search": 0.0}
     if p.shape[0]:
-        fine = _floor_edge(default_edge(pts, k, cap) if edge is None else float(edge), side)
-        grid, xs, keys, perm = _sorted_cloud(pts, p, fine, "knn_mean_distance")
+        fine = floor_edge(default_edge(pts, k, cap) if edge is None else float(edge), side)
+        sc = sort_into_cells(pts, fine, "knn_mean_distance", extent=p)
         torch.cuda.synchronize(dev)
         t1 = time.perf_counter()
-        full = max_ring(cap, fine)
-        ops.cloud_knn_mean(xs, keys, perm, grid, k, cap, min(full, FINE_RINGS), mean, flag)
+        plan = two_grid_plan(cap, fine)
+        ops.cloud_knn_mean(sc.xyz, sc.keys, sc.perm, sc.grid, k, cap, plan.fine_rings, mean, flag)
         stats["edge"] = fine
-        if full > FINE_RINGS:
+        if plan.coarse_edge is not None:
             todo = torch.nonzero(flag == RINGS_USED_UP).squeeze(1)
             stats["second_pass"] = int(todo.numel())
             if todo.numel():
                 t2 = time.perf_counter()
-                coarse = _floor_edge(max(cap / COARSE_SHARE, fine), side)
-                grid2, xs2, keys2, perm2 = _sorted_cloud(pts, p, coarse, "knn_mean_distance")
-                where = torch.empty_like(perm2)
-                where[perm2] = torch.arange(n, device=dev, dtype=torch.int64)          # original index -> sorted position
+                # plan.coarse_edge >= fine, which floor_edge has already raised to what the key allows: no second floor_edge
+                sc2 = sort_into_cells(pts, plan.coarse_edge, "knn_mean_distance", extent=p)
+                where = torch.empty_like(sc2.perm)
+                where[sc2.perm] = torch.arange(n, device=dev, dtype=torch.int64)          # original index -> sorted position
                 index = torch.sort(where[todo]).values.contiguous()                     # neighbouring lanes, neighbouring cells
                 torch.cuda.synchronize(dev)
                 t1 += time.perf_counter() - t2                                           # the second sort counts as sort time
-                ops.cloud_knn_mean(xs2, keys2, perm2, grid2, k, cap, max_ring(cap, coarse), mean, flag, index=index)
-                stats["coarse_edge"] = coarse
+                ops.cloud_knn_mean(sc2.xyz, sc2.keys, sc2.perm, sc2.grid, k, cap, plan.coarse_rings, mean, flag, index=index)
+                stats["coarse_edge"] = plan.coarse_edge
         torch.cuda.synchronize(dev)
         stats["seconds_sort"] = t1 - t0
         stats["seconds_search"] = time.perf_counter() - t1
@@ -164,7 +141,7 @@ def statistical_outlier_mask(xyz: Tensor, k: int = 20, std_ratio: float = 2.0, c
     threshold, kept, removed."""
     if not (std_ratio >= 0 and math.isfinite(std_ratio)):
         raise ValueError(f"statistical_outlier_mask: std_ratio must be finite and >= 0, got {std_ratio}")
-    cap = default_cap(_points("statistical_outlier_mask", xyz)) if cap is None else float(cap)
+    cap = default_cap(points("statistical_outlier_mask", xyz)) if cap is None else float(cap)
     stats: Dict[str, object] = {}
     m, isolated = knn_mean_distance(xyz, k, cap, info=stats)
     ok = ~isolated
@@ -184,7 +161,7 @@ def statistical_outlier_mask(xyz: Tensor, k: int = 20, std_ratio: float = 2.0, c
 def radius_neighbour_count(xyz: Tensor, radius: float, limit: int, info: Optional[dict] = None) -> Tensor:
     """int32 [n] = min(number of OTHER points with d2 <= radius * radius, limit), on a grid whose cells are a hair wider than
     ``radius`` (27 cells per query; the walk leaves early once ``limit`` is reached)"""
-    pts = _points("radius_neighbour_count", xyz)
+    pts = points("radius_neighbour_count", xyz)
     if not (radius > 0 and math.isfinite(radius)):
         raise ValueError(f"radius_neighbour_count: radius must be positive and finite, got {radius}")
     if int(limit) < 1:
@@ -192,15 +169,14 @@ def radius_neighbour_count(xyz: Tensor, radius: float, limit: int, info: Optiona
     n, dev = pts.shape[0], pts.device
     t0 = time.perf_counter()
     count = torch.zeros((n,), device=dev, dtype=torch.int32)
-    finite = torch.isfinite(pts).all(1)
-    p, side = _extent(pts, finite)
+    p, side = finite_extent(pts)
     stats = {"edge": None, "non_finite": n - int(p.shape[0]), "seconds_sort": 0.0, "seconds_search": 0.0}
     if p.shape[0]:
-        edge = _floor_edge(radius * RADIUS_EDGE, side)
-        grid, xs, keys, perm = _sorted_cloud(pts, p, edge, "radius_neighbour_count")
+        edge = floor_edge(radius * RADIUS_EDGE, side)
+        sc = sort_into_cells(pts, edge, "radius_neighbour_count", extent=p)
         torch.cuda.synchronize(dev)
         t1 = time.perf_counter()
-        ops.cloud_radius_count(xs, keys, perm, grid, radius, int(limit), count)
+        ops.cloud_radius_count(sc.xyz, sc.keys, sc.perm, sc.grid, radius, int(limit), count)
         torch.cuda.synchronize(dev)
         stats.update(edge=edge, seconds_sort=t1 - t0, seconds_search=time.perf_counter() - t1)
     if info is not None:

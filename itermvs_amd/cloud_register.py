@@ -3,8 +3,8 @@ training scene -- with every pass over points on the GPU (csrc/cloud_register.hi
 the benchmark's scoring script (align, crop to the scene's polygon volume, voxel-downsample, three rounds of ICP with scale,
 nearest-neighbour distances in both directions, counts below tau) without Open3D.
 
-All geometry is fp64 on the float32 coordinates of the PLY files.  Sorting by cell key, prefix sums, compaction and the
-transform of a kept cloud are torch plumbing; the crop, the voxel mean, the nearest-neighbour index, the sums of the similarity
+All geometry is fp64 on the float32 coordinates of the PLY files.  Sorting by cell key (``cloud_grid.sort_into_cells``, for the
+voxels and for the ICP targets alike), prefix sums, compaction and the transform of a kept cloud are torch plumbing; the crop, the voxel mean, the nearest-neighbour index, the sums of the similarity
 fit and the capped distances are HIP.  The 3x3 SVD runs in numpy on the host, from 18 doubles read back per ICP iteration.
 
 Differences from the Open3D script: voxel means come out in ascending voxel-key order (Open3D: a hash
@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import cloud_eval, ops
+from .cloud_grid import max_ring, points, sort_into_cells
 from .ops import CloudGrid
 
 Tensor = torch.Tensor
@@ -88,7 +89,7 @@ def read_trajectory_log(path: str) -> np.ndarray:
 
 def crop(pts: Tensor, volume: SelectionVolume, T=None) -> Tensor:
     """bool [n]: T * p (T = identity when None) lies inside ``volume``; a non-finite point is outside"""
-    pts = cloud_eval._points("crop", pts)
+    pts = points("crop", pts)
     if pts.shape[0] == 0:
         return torch.zeros((0,), device=pts.device, dtype=torch.bool)
     return ops.cloud_crop(pts, np.eye(4) if T is None else T, volume.axis, volume.axis_min, volume.axis_max, volume.polygon).bool()
@@ -106,25 +107,18 @@ def voxel_down_sample(pts: Tensor, voxel: float) -> Tensor:
     origin = min_bound - voxel / 2: the mean of the voxel's points (fp64 sum in index order, one rounding).  Output order:
     ascending voxel key (x-major), not Open3D's hash-map order.  Non-finite points are dropped.  The prefix sum of the segment
     heads is torch.cumsum (plumbing); keys, heads and means are HIP."""
-    pts = cloud_eval._points("voxel_down_sample", pts)
+    pts = points("voxel_down_sample", pts)
     if not (voxel > 0 and math.isfinite(voxel)):
         raise ValueError(f"voxel_down_sample: voxel must be positive, got {voxel}")
-    pts = pts[torch.isfinite(pts).all(1)]
-    if pts.shape[0] == 0:
-        return pts
-    lo, hi = pts.min(0).values.double().cpu().numpy(), pts.max(0).values.double().cpu().numpy()
-    origin = lo - voxel / 2
-    dims = [int(math.floor((float(hi[a]) - float(origin[a])) / voxel)) + 1 for a in range(3)]
-    if max(dims) > cloud_eval.MAX_CELL_DIM:
-        raise ValueError(f"voxel_down_sample: the cloud spans {dims} voxels of {voxel}; at most {cloud_eval.MAX_CELL_DIM} per axis")
-    grid = CloudGrid(tuple(float(v) for v in origin), tuple(dims), float(voxel))
-    keys, perm = torch.sort(ops.cloud_cell_keys(pts, grid), stable=True)
-    head = ops.cloud_voxel_heads(keys)
+    sc = sort_into_cells(pts, voxel, "voxel_down_sample", pad=voxel / 2, stable=True)       # stable: the sums run in index order
+    if sc.xyz.shape[0] == 0:
+        return sc.xyz
+    head = ops.cloud_voxel_heads(sc.keys)
     rank = torch.cumsum(head, 0, dtype=torch.int64) - 1
     n_out = int(rank[-1]) + 1
     if n_out < 1:
-        return pts[:0]
-    return ops.cloud_voxel_mean(pts[perm].contiguous(), keys, rank, n_out)
+        return sc.xyz[:0]
+    return ops.cloud_voxel_mean(sc.xyz, sc.keys, rank, n_out)
 
 
 def uniform_down_sample(pts: Tensor, every_k: int) -> Tensor:
@@ -156,22 +150,11 @@ def umeyama(sums, with_scale: bool = True) -> np.ndarray:
     return out
 
 
-def max_ring(max_dist: float, edge: float) -> int:
-    """the number of rings that makes ``ops.cloud_nn_index`` exact within ``max_dist`` on cells of ``edge``"""
-    return cloud_eval.max_ring(max_dist, edge)
-
-
 def build_target_grid(target: Tensor, edge: float) -> TargetGrid:
     """sort the finite points of float32 [nt,3] ``target`` into cells of ``edge`` for ``icp``"""
-    target = cloud_eval._points("build_target_grid", target)
-    finite = torch.nonzero(torch.isfinite(target).all(1)).squeeze(1)
-    t = target[finite]
-    if t.shape[0] == 0:
-        e = torch.zeros((0,), device=target.device, dtype=torch.int64)
-        return TargetGrid(target, t, e, e, CloudGrid((0.0, 0.0, 0.0), (1, 1, 1), float(edge)))
-    grid = cloud_eval.grid_for(t, edge, "build_target_grid")
-    keys, perm = torch.sort(ops.cloud_cell_keys(t, grid))
-    return TargetGrid(target, t[perm].contiguous(), keys, finite[perm].contiguous(), grid)
+    target = points("build_target_grid", target)
+    sc = sort_into_cells(target, edge, "build_target_grid")
+    return TargetGrid(target, sc.xyz, sc.keys, sc.perm, sc.grid)
 
 
 def icp(source: Tensor, target_grid: TargetGrid, init=None, max_dist: float = 1.0, max_iter: int = 20, rel_fitness: float = 1e-6,
@@ -181,7 +164,7 @@ def icp(source: Tensor, target_grid: TargetGrid, init=None, max_dist: float = 1.
     matches / n, rmse = sqrt(sum d2 / matches); stop when both changed by less than their thresholds since the previous
     evaluation, after ``max_iter`` updates, or with fewer than 3 matches; else T <- umeyama(sums) @ T.  Returns (T, fitness,
     rmse, updates applied); fitness and rmse belong to the returned T."""
-    source = cloud_eval._points("icp", source)
+    source = points("icp", source)
     T = np.eye(4) if init is None else np.array(init, dtype=np.float64)
     n = source.shape[0]
     if n == 0:
@@ -263,7 +246,7 @@ def evaluate_scene(pred: Tensor, gt: Tensor, volume: SelectionVolume, init: np.n
     False), then crop both clouds, voxel-downsample both
     at tau / 2, distances in both directions capped at plot_stretch * tau, precision = #(d_pred->gt < tau) / n_pred, recall =
     #(d_gt->pred < tau) / n_gt, F = 2PR / (P + R) (0 when both are 0) and both cumulative curves on 500 bins."""
-    pred, gt = cloud_eval._points("evaluate_scene", pred), cloud_eval._points("evaluate_scene", gt)
+    pred, gt = points("evaluate_scene", pred), points("evaluate_scene", gt)
     if not (tau > 0 and math.isfinite(tau)):
         raise ValueError(f"evaluate_scene: tau must be positive, got {tau}")
     T = np.array(init, dtype=np.float64).reshape(4, 4)

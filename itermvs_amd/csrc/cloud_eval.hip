@@ -61,8 +61,9 @@ __global__ void __launch_bounds__(kCloudBlock) cloud_reduce_round_kernel(const f
         __hip_atomic_store(&state[i], kRemoved, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return;
     }
-    const int cz = (int)(key % g.nz), cy = (int)((key / g.nz) % g.ny), cx = (int)(key / g.nz / g.ny);
-    const double qx = (double)xyz[i * 3 + 0], qy = (double)xyz[i * 3 + 1], qz = (double)xyz[i * 3 + 2];
+    int cx, cy, cz;
+    cell_from_key(key, g, cx, cy, cz);
+    const CloudPoint q = load_point(xyz, i);
     const int my = rank[i];
     const int x0 = cx > 0 ? cx - 1 : 0, x1 = cx < g.nx - 1 ? cx + 1 : g.nx - 1;
     const int y0 = cy > 0 ? cy - 1 : 0, y1 = cy < g.ny - 1 ? cy + 1 : g.ny - 1;
@@ -72,7 +73,7 @@ __global__ void __launch_bounds__(kCloudBlock) cloud_reduce_round_kernel(const f
         for (int y = y0; y <= y1; ++y) {
             const long long row = ((long long)x * g.ny + y) * g.nz, last = row + z1;
             for (long long j = lower_bound(keys, n, row + z0); j < n && keys[j] <= last; ++j) {
-                if (j == i || rank[j] >= my || dist2(qx, qy, qz, xyz + j * 3) > dst2) continue;
+                if (j == i || rank[j] >= my || dist2(q.x, q.y, q.z, xyz + j * 3) > dst2) continue;
                 const int s = __hip_atomic_load(&state[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (s == kKept) {                          // reducePts_haa.m:27: an earlier kept point removes this one
                     __hip_atomic_store(&state[i], kRemoved, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -141,9 +142,9 @@ using namespace itermvs;
 extern "C" int itermvs_cloud_cell_keys(const float* xyz, int64_t n, double ox, double oy, double oz, int32_t nx, int32_t ny,
                                        int32_t nz, double edge, int64_t* keys, void* stream) {
     ITERMVS_RETURN_IF(!xyz || !keys, ITERMVS_ERR_NULL);
-    const int bad = check_grid(n, ox, oy, oz, nx, ny, nz, edge);
+    CloudGrid g;
+    const int bad = check_grid(n, ox, oy, oz, nx, ny, nz, edge, &g);
     ITERMVS_RETURN_IF(bad, bad);
-    const CloudGrid g{ox, oy, oz, edge, nx, ny, nz};
     return flat_launch<cloud_cell_keys_kernel, kCloudBlock>({n, kCloudMaxPoints}, (hipStream_t)stream, xyz, (long long)n, g, (long long*)keys);
 }
 
@@ -151,10 +152,10 @@ extern "C" int itermvs_cloud_reduce_round(const float* xyz_sorted, const int64_t
                                           int64_t n, double ox, double oy, double oz, int32_t nx, int32_t ny, int32_t nz,
                                           double edge, double dst, int32_t* state, int32_t* undecided, void* stream) {
     ITERMVS_RETURN_IF(!xyz_sorted || !keys_sorted || !rank_sorted || !state || !undecided, ITERMVS_ERR_NULL);
-    const int bad = check_grid(n, ox, oy, oz, nx, ny, nz, edge);
+    CloudGrid g;
+    const int bad = check_grid(n, ox, oy, oz, nx, ny, nz, edge, &g);
     ITERMVS_RETURN_IF(bad, bad);
     ITERMVS_RETURN_IF(!isfinite(dst) || !(dst > 0.0) || edge < dst, ITERMVS_ERR_DIMS);      // 27 cells must hold the radius
-    const CloudGrid g{ox, oy, oz, edge, nx, ny, nz};
     return flat_launch<cloud_reduce_round_kernel, kCloudBlock>({n, kCloudMaxPoints}, (hipStream_t)stream, xyz_sorted,
         (const long long*)keys_sorted, (const int*)rank_sorted, (long long)n, g, dst * dst, (int*)state, (int*)undecided);
 }
@@ -165,15 +166,15 @@ extern "C" int itermvs_cloud_nn_distance(const float* q_from, int64_t nq, const 
                                          double cap, int32_t rings, double* best_d2, uint8_t* done, double* dist, void* stream) {
     ITERMVS_RETURN_IF(!q_from || !to_sorted || !keys_sorted || !region || !best_d2 || !done || !dist, ITERMVS_ERR_NULL);
     ITERMVS_RETURN_IF(nq < 1 || nq > kCloudMaxPoints || (index && (n_index < 1 || n_index > nq)), ITERMVS_ERR_DIMS);
-    const int bad = check_grid(nt, ox, oy, oz, nx, ny, nz, edge);
+    CloudGrid g;
+    const int bad = check_grid(nt, ox, oy, oz, nx, ny, nz, edge, &g);
     ITERMVS_RETURN_IF(bad, bad);
-    ITERMVS_RETURN_IF(!isfinite(cap) || !(cap > 0.0) || rings < 1 || rings > kMaxCellDim, ITERMVS_ERR_DIMS);
+    ITERMVS_RETURN_IF(check_walk(cap, rings), ITERMVS_ERR_DIMS);
     CloudRegion reg;
     for (int a = 0; a < 3; ++a) {
         reg.lo[a] = region[a];                             // host memory: BB(1,:) and (BB(1,:) + Range * cap) + cap
         reg.hi[a] = region[3 + a];
     }
-    const CloudGrid g{ox, oy, oz, edge, nx, ny, nz};
     return flat_launch<cloud_nn_distance_kernel, kCloudBlock>({index ? n_index : nq, kCloudMaxPoints}, (hipStream_t)stream, q_from, (long long)nq,
         (const long long*)index, (long long)n_index, to_sorted, (const long long*)keys_sorted, (long long)nt, g, reg, cap, rings, best_d2, done,
         dist);

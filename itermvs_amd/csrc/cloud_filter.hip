@@ -86,14 +86,15 @@ __global__ void __launch_bounds__(kCloudBlock) cloud_knn_mean_kernel(const float
         flag[o] = kKnnIsolated;
         return;
     }
-    const int cz = (int)(key % g.nz), cy = (int)((key / g.nz) % g.ny), cx = (int)(key / g.nz / g.ny);
-    const double qx = (double)xyz[i * 3 + 0], qy = (double)xyz[i * 3 + 1], qz = (double)xyz[i * 3 + 2];
+    int cx, cy, cz;
+    cell_from_key(key, g, cx, cy, cz);
+    const CloudPoint q = load_point(xyz, i);
     KNearest<K> best;
 #pragma unroll
     for (int t = 0; t < K; ++t) best.v[t] = t < K - k ? -INFINITY : INFINITY;
     best.d2 = INFINITY;
     best.self = i;
-    const bool found = ring_walk(xyz, keys, n, g, cx, cy, cz, qx, qy, qz, cap, rings, best);
+    const bool found = ring_walk(xyz, keys, n, g, cx, cy, cz, q.x, q.y, q.z, cap, rings, best);
     double m = INFINITY;
     uint8_t f = kKnnRingsUsedUp;
     if (found) {
@@ -123,10 +124,11 @@ __global__ void __launch_bounds__(kCloudBlock) cloud_radius_count_kernel(const f
         count[o] = 0;
         return;
     }
-    const int cz = (int)(key % g.nz), cy = (int)((key / g.nz) % g.ny), cx = (int)(key / g.nz / g.ny);
-    const double qx = (double)xyz[i * 3 + 0], qy = (double)xyz[i * 3 + 1], qz = (double)xyz[i * 3 + 2];
+    int cx, cy, cz;
+    cell_from_key(key, g, cx, cy, cz);
+    const CloudPoint q = load_point(xyz, i);
     RadiusCount best{r * r, r * r, i, 0, limit};
-    ring_walk(xyz, keys, n, g, cx, cy, cz, qx, qy, qz, r, rings, best);       // rings reach r: the walk always ends on a bound
+    ring_walk(xyz, keys, n, g, cx, cy, cz, q.x, q.y, q.z, r, rings, best);       // rings reach r: the walk always ends on a bound
     count[o] = best.count;
 }
 
@@ -146,11 +148,11 @@ extern "C" int itermvs_cloud_knn_mean(const float* xyz_sorted, const int64_t* ke
                                       int32_t ny, int32_t nz, double edge, int32_t k, double cap, int32_t rings, double* mean,
                                       uint8_t* flag, void* stream) {
     ITERMVS_RETURN_IF(!xyz_sorted || !keys_sorted || !perm || !mean || !flag, ITERMVS_ERR_NULL);
-    const int bad = check_grid(n, ox, oy, oz, nx, ny, nz, edge);
+    CloudGrid g;
+    const int bad = check_grid(n, ox, oy, oz, nx, ny, nz, edge, &g);
     ITERMVS_RETURN_IF(bad, bad);
     ITERMVS_RETURN_IF(k < 1 || k > kKnnMaxK || n <= k || (index && (n_index < 1 || n_index > n)), ITERMVS_ERR_DIMS);
-    ITERMVS_RETURN_IF(!isfinite(cap) || !(cap > 0.0) || rings < 1 || rings > kMaxCellDim, ITERMVS_ERR_DIMS);
-    const CloudGrid g{ox, oy, oz, edge, nx, ny, nz};
+    ITERMVS_RETURN_IF(check_walk(cap, rings), ITERMVS_ERR_DIMS);
     const FlatItems items{index ? n_index : n, kCloudMaxPoints};
     const hipStream_t s = (hipStream_t)stream;
 #define ITERMVS_KNN_LAUNCH(K)                                                                                                     \
@@ -166,12 +168,12 @@ extern "C" int itermvs_cloud_radius_count(const float* xyz_sorted, const int64_t
                                           double ox, double oy, double oz, int32_t nx, int32_t ny, int32_t nz, double edge,
                                           double r, int32_t limit, int32_t* count, void* stream) {
     ITERMVS_RETURN_IF(!xyz_sorted || !keys_sorted || !perm || !count, ITERMVS_ERR_NULL);
-    const int bad = check_grid(n, ox, oy, oz, nx, ny, nz, edge);
+    CloudGrid g;
+    const int bad = check_grid(n, ox, oy, oz, nx, ny, nz, edge, &g);
     ITERMVS_RETURN_IF(bad, bad);
     ITERMVS_RETURN_IF(!isfinite(r) || !(r > 0.0) || limit < 1, ITERMVS_ERR_DIMS);
     const int rings = rings_to_reach(r, edge, kRadiusMaxRings);
     ITERMVS_RETURN_IF(rings < 1, ITERMVS_ERR_DIMS);            // cells far smaller than r: a bad grid for this search
-    const CloudGrid g{ox, oy, oz, edge, nx, ny, nz};
     return flat_launch<cloud_radius_count_kernel, kCloudBlock>({n, kCloudMaxPoints}, (hipStream_t)stream, xyz_sorted,
         (const long long*)keys_sorted, (const long long*)perm, (long long)n, g, r, (int)limit, rings, (int*)count);
 }

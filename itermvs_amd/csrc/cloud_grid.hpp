@@ -1,5 +1,6 @@
-// The uniform grid of the cloud searches, shared by cloud_eval.hip (DTU) and cloud_register.hip (Tanks and Temples): the cell
-// key, the binary search over the sorted keys, the squared distance and the ring walk with its stop bounds.
+// The uniform grid of the cloud searches, shared by cloud_eval.hip (DTU), cloud_register.hip (Tanks and Temples) and
+// cloud_filter.hip (outlier removal): the cell key, the binary search over the sorted keys, the squared distance, the ring walk
+// with its stop bounds, and the entry points' checks of a grid and a walk.  Host counterpart: itermvs_amd/cloud_grid.py.
 //
 // cell = floor((p - origin) / edge) per axis, key = (cx * ny + cy) * nz + cz (int64; every dimension <= 2^21, so the key fits
 // 63 bits).  The targets are sorted by key; the cells z0..z1 of one (cx, cy) row are contiguous in key order, so one binary
@@ -29,8 +30,23 @@ struct CloudGrid {
     int nx, ny, nz;
 };
 
+struct CloudPoint {
+    double x, y, z;
+};
+
 __device__ __forceinline__ double cell_of(double p, double o, double edge) {
     return floor((p - o) / edge);
+}
+
+// the cell a key (not kNoKey) names
+__device__ __forceinline__ void cell_from_key(long long key, const CloudGrid& g, int& cx, int& cy, int& cz) {
+    cz = (int)(key % g.nz);
+    cy = (int)((key / g.nz) % g.ny);
+    cx = (int)(key / g.nz / g.ny);
+}
+
+__device__ __forceinline__ CloudPoint load_point(const float* __restrict__ xyz, long long i) {
+    return CloudPoint{(double)xyz[i * 3 + 0], (double)xyz[i * 3 + 1], (double)xyz[i * 3 + 2]};
 }
 
 // first position in keys[0 : n) whose key is >= want; n < 2^31, so 32 halvings always finish
@@ -113,11 +129,18 @@ static inline bool finite_all(double a, double b, double c, double d) {
     return isfinite(a) && isfinite(b) && isfinite(c) && isfinite(d);
 }
 
-// ITERMVS_OK or the error of a grid description; n is the number of points of the launch
-static inline int check_grid(long long n, double ox, double oy, double oz, int nx, int ny, int nz, double edge) {
+// ITERMVS_OK and the grid in *g, or the error of a grid description; n is the number of points of the launch
+static inline int check_grid(long long n, double ox, double oy, double oz, int nx, int ny, int nz, double edge, CloudGrid* g) {
     ITERMVS_RETURN_IF(n < 1 || n > kCloudMaxPoints, ITERMVS_ERR_DIMS);
     ITERMVS_RETURN_IF(!finite_all(ox, oy, oz, edge) || !(edge > 0.0), ITERMVS_ERR_DIMS);
     ITERMVS_RETURN_IF(nx < 1 || ny < 1 || nz < 1 || nx > kMaxCellDim || ny > kMaxCellDim || nz > kMaxCellDim, ITERMVS_ERR_DIMS);
+    *g = CloudGrid{ox, oy, oz, edge, nx, ny, nz};
+    return ITERMVS_OK;
+}
+
+// ITERMVS_OK or the error of a ring walk's cap and number of rings
+static inline int check_walk(double cap, int rings) {
+    ITERMVS_RETURN_IF(!isfinite(cap) || !(cap > 0.0) || rings < 1 || rings > kMaxCellDim, ITERMVS_ERR_DIMS);
     return ITERMVS_OK;
 }
 

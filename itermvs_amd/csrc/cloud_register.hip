@@ -296,12 +296,12 @@ extern "C" int itermvs_cloud_nn_index(const float* q, int64_t nq, const double* 
                                       int64_t* idx, double* d2, void* stream) {
     ITERMVS_RETURN_IF(!q || !T || !idx || !d2 || (nt > 0 && (!to_sorted || !keys_sorted || !perm)), ITERMVS_ERR_NULL);
     ITERMVS_RETURN_IF(nq < 1 || nq > kCloudMaxPoints || nt < 0, ITERMVS_ERR_DIMS);
-    const int bad = check_grid(nt > 0 ? nt : 1, ox, oy, oz, nx, ny, nz, edge);
+    CloudGrid g;
+    const int bad = check_grid(nt > 0 ? nt : 1, ox, oy, oz, nx, ny, nz, edge, &g);
     ITERMVS_RETURN_IF(bad, bad);
-    ITERMVS_RETURN_IF(!isfinite(max_dist) || !(max_dist > 0.0) || rings < 1 || rings > kMaxCellDim, ITERMVS_ERR_DIMS);
+    ITERMVS_RETURN_IF(check_walk(max_dist, rings), ITERMVS_ERR_DIMS);
     Transform tr;
     ITERMVS_RETURN_IF(!read_transform(T, tr), ITERMVS_ERR_DIMS);
-    const CloudGrid g{ox, oy, oz, edge, nx, ny, nz};
     return flat_launch<cloud_nn_index_kernel, kCloudBlock>({nq, kCloudMaxPoints}, (hipStream_t)stream, q, (long long)nq, tr, to_sorted,
         (const long long*)keys_sorted, (const long long*)perm, (long long)nt, g, max_dist, max_dist * max_dist, (int)rings, (long long*)idx, d2);
 }

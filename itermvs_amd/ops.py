@@ -1609,6 +1609,13 @@ def _cloud(what: str, t: Tensor, name: str, dtype=torch.float32, shape_tail: tup
     return t
 
 
+def _cloud_flat(what: str, m: int, *tensors) -> None:
+    """every (tensor, dtype, name) is a contiguous flat device tensor of that dtype with exactly ``m`` elements"""
+    for t, dt, name in tensors:
+        if _cloud(what, t, name, dt, ()).numel() != m:
+            raise RuntimeError(f"{what}: {name} must have {m} elements, got {t.numel()}")
+
+
 def cloud_cell_keys(xyz: Tensor, grid: CloudGrid) -> Tensor:
     """itermvs_cloud_cell_keys: int64 [n] cell keys of float32 [n,3] points on ``grid``; INT64_MAX for a point that is not
     finite or outside the grid.  An extent that does not fit the key (a dimension above 2^21) raises."""
@@ -1626,10 +1633,9 @@ def cloud_reduce_round(xyz_sorted: Tensor, keys_sorted: Tensor, rank_sorted: Ten
     int32 [n] (0 undecided, 1 kept, 2 removed) is updated in place; ``undecided`` (int32, one element, zeroed by the caller) counts
     the points the round leaves undecided.  Nothing is read back."""
     n = _cloud("cloud_reduce_round", xyz_sorted, "xyz_sorted").shape[0]
-    for t, dt, name, m in ((keys_sorted, torch.int64, "keys_sorted", n), (rank_sorted, torch.int32, "rank_sorted", n),
-                           (state, torch.int32, "state", n), (undecided, torch.int32, "undecided", 1)):
-        if _cloud("cloud_reduce_round", t, name, dt, ()).numel() != m:
-            raise RuntimeError(f"cloud_reduce_round: {name} must have {m} elements, got {t.numel()}")
+    _cloud_flat("cloud_reduce_round", n, (keys_sorted, torch.int64, "keys_sorted"), (rank_sorted, torch.int32, "rank_sorted"),
+                (state, torch.int32, "state"))
+    _cloud_flat("cloud_reduce_round", 1, (undecided, torch.int32, "undecided"))
     check(_lib.load().itermvs_cloud_reduce_round(xyz_sorted.data_ptr(), keys_sorted.data_ptr(), rank_sorted.data_ptr(), n,
                                                  *grid.args(), float(dst), state.data_ptr(), undecided.data_ptr(), _stream()),
           "itermvs_cloud_reduce_round")
@@ -1643,10 +1649,8 @@ def cloud_nn_distance(q_from: Tensor, to_sorted: Tensor, keys_sorted: Tensor, gr
     place; ``index``: int64 list of the queries to look at (default: all).  Nothing is read back."""
     nq = _cloud("cloud_nn_distance", q_from, "q_from").shape[0]
     nt = _cloud("cloud_nn_distance", to_sorted, "to_sorted").shape[0]
-    for t, dt, name, m in ((keys_sorted, torch.int64, "keys_sorted", nt), (best_d2, torch.float64, "best_d2", nq),
-                           (done, torch.uint8, "done", nq), (dist, torch.float64, "dist", nq)):
-        if _cloud("cloud_nn_distance", t, name, dt, ()).numel() != m:
-            raise RuntimeError(f"cloud_nn_distance: {name} must have {m} elements, got {t.numel()}")
+    _cloud_flat("cloud_nn_distance", nt, (keys_sorted, torch.int64, "keys_sorted"))
+    _cloud_flat("cloud_nn_distance", nq, (best_d2, torch.float64, "best_d2"), (done, torch.uint8, "done"), (dist, torch.float64, "dist"))
     if index is not None:
         _cloud("cloud_nn_distance", index, "index", torch.int64, ())
     if len(region) != 6:
@@ -1710,9 +1714,7 @@ def cloud_voxel_mean(xyz_sorted: Tensor, keys_sorted: Tensor, rank: Tensor, n_ou
     """itermvs_cloud_voxel_mean: float32 [n_out,3] = per run of equal keys the mean of its points (fp64 sum in sorted order, one
     rounding), at the run's ``rank`` (int64 [n]: inclusive prefix sum of the heads, minus 1)"""
     n = _cloud("cloud_voxel_mean", xyz_sorted, "xyz_sorted").shape[0]
-    for t, name in ((keys_sorted, "keys_sorted"), (rank, "rank")):
-        if _cloud("cloud_voxel_mean", t, name, torch.int64, ()).numel() != n:
-            raise RuntimeError(f"cloud_voxel_mean: {name} must have {n} elements, got {t.numel()}")
+    _cloud_flat("cloud_voxel_mean", n, (keys_sorted, torch.int64, "keys_sorted"), (rank, torch.int64, "rank"))
     out = torch.zeros((max(int(n_out), 0), 3), device=xyz_sorted.device, dtype=torch.float32)
     check(_lib.load().itermvs_cloud_voxel_mean(xyz_sorted.data_ptr(), keys_sorted.data_ptr(), rank.data_ptr(), n, int(n_out),
                                                out.data_ptr(), _stream()), "itermvs_cloud_voxel_mean")
@@ -1726,9 +1728,7 @@ def cloud_nn_index(q: Tensor, T, to_sorted: Tensor, keys_sorted: Tensor, perm: T
     and perm int64 [nt] in key order on ``grid``; nt may be 0."""
     nq = _cloud("cloud_nn_index", q, "q").shape[0]
     nt = _cloud("cloud_nn_index", to_sorted, "to_sorted").shape[0]
-    for t, name in ((keys_sorted, "keys_sorted"), (perm, "perm")):
-        if _cloud("cloud_nn_index", t, name, torch.int64, ()).numel() != nt:
-            raise RuntimeError(f"cloud_nn_index: {name} must have {nt} elements, got {t.numel()}")
+    _cloud_flat("cloud_nn_index", nt, (keys_sorted, torch.int64, "keys_sorted"), (perm, torch.int64, "perm"))
     idx = torch.empty((nq,), device=q.device, dtype=torch.int64)
     d2 = torch.empty((nq,), device=q.device, dtype=torch.float64)
     check(_lib.load().itermvs_cloud_nn_index(q.data_ptr(), nq, _transform("cloud_nn_index", T), _ptr(to_sorted) if nt else None,
@@ -1750,9 +1750,7 @@ def cloud_umeyama_sums(q: Tensor, T, idx: Tensor, d2: Tensor, target: Tensor) ->
     correspondences idx[i] >= 0 with p = T * q_i and t = target[idx[i]] (the unsorted targets).  Nothing is read back."""
     n = _cloud("cloud_umeyama_sums", q, "q").shape[0]
     nt = _cloud("cloud_umeyama_sums", target, "target").shape[0]
-    for t, dt, name in ((idx, torch.int64, "idx"), (d2, torch.float64, "d2")):
-        if _cloud("cloud_umeyama_sums", t, name, dt, ()).numel() != n:
-            raise RuntimeError(f"cloud_umeyama_sums: {name} must have {n} elements, got {t.numel()}")
+    _cloud_flat("cloud_umeyama_sums", n, (idx, torch.int64, "idx"), (d2, torch.float64, "d2"))
     partials = torch.empty((max(cloud_umeyama_groups(n), 1) if n else 1, 18), device=q.device, dtype=torch.float64)
     sums = torch.empty((18,), device=q.device, dtype=torch.float64)
     check(_lib.load().itermvs_cloud_umeyama_sums(q.data_ptr(), n, _transform("cloud_umeyama_sums", T), idx.data_ptr(), d2.data_ptr(),
@@ -1768,10 +1766,8 @@ def cloud_knn_mean(xyz_sorted: Tensor, keys_sorted: Tensor, perm: Tensor, grid: 
     ``index`` (int64): flag 0 = settled (mean = the mean distance to the k nearest other points), 1 = isolated (fewer than k within
     ``cap``; mean +Inf), 2 = rings used up (mean +Inf; repeat on a coarser grid).  Nothing is read back."""
     n = _cloud("cloud_knn_mean", xyz_sorted, "xyz_sorted").shape[0]
-    for t, dt, name in ((keys_sorted, torch.int64, "keys_sorted"), (perm, torch.int64, "perm"), (mean, torch.float64, "mean"),
-                        (flag, torch.uint8, "flag")):
-        if _cloud("cloud_knn_mean", t, name, dt, ()).numel() != n:
-            raise RuntimeError(f"cloud_knn_mean: {name} must have {n} elements, got {t.numel()}")
+    _cloud_flat("cloud_knn_mean", n, (keys_sorted, torch.int64, "keys_sorted"), (perm, torch.int64, "perm"),
+                (mean, torch.float64, "mean"), (flag, torch.uint8, "flag"))
     if index is not None:
         _cloud("cloud_knn_mean", index, "index", torch.int64, ())
     check(_lib.load().itermvs_cloud_knn_mean(_ptr(xyz_sorted), _ptr(keys_sorted), _ptr(perm), n, _ptr(index),
@@ -1784,9 +1780,8 @@ def cloud_radius_count(xyz_sorted: Tensor, keys_sorted: Tensor, perm: Tensor, gr
     """itermvs_cloud_radius_count: count int32 [n], in the caller's order (at perm[position]) = min(number of other points with
     d2 <= radius * radius, limit) for every point of a key-sorted cloud.  Nothing is read back."""
     n = _cloud("cloud_radius_count", xyz_sorted, "xyz_sorted").shape[0]
-    for t, dt, name in ((keys_sorted, torch.int64, "keys_sorted"), (perm, torch.int64, "perm"), (count, torch.int32, "count")):
-        if _cloud("cloud_radius_count", t, name, dt, ()).numel() != n:
-            raise RuntimeError(f"cloud_radius_count: {name} must have {n} elements, got {t.numel()}")
+    _cloud_flat("cloud_radius_count", n, (keys_sorted, torch.int64, "keys_sorted"), (perm, torch.int64, "perm"),
+                (count, torch.int32, "count"))
     check(_lib.load().itermvs_cloud_radius_count(_ptr(xyz_sorted), _ptr(keys_sorted), _ptr(perm), n, *grid.args(), float(radius),
                                                  int(limit), _ptr(count), _stream()), "itermvs_cloud_radius_count")
 

@@ -201,9 +201,6 @@ def test_above_plane_and_host_side_helpers():
     assert lo.tolist() == [0.0, 0.0, 0.0] and hi.tolist() == [180.0, 60.0, 120.0]
     lo, hi = CE.covered_region([[0.0, 0.0, 0.0], [10.0, -1.0, 10.0]], 60.0)                       # a negative Range: no block at all
     assert (hi == lo).all()
-    for cap, edge in ((60.0, 1.0), (60.0, 7.5), (4.0, 1.0), (1.0, 3.0)):
-        r = CE.max_ring(cap, edge)
-        assert (r - 1) * edge * CE.RING_SHRINK >= cap > (r - 2) * edge * CE.RING_SHRINK
     rank = CE.inverse_permutation(torch.tensor([2, 0, 1]), 3)
     assert rank.dtype == torch.int32 and rank.tolist() == [1, 2, 0]
     for bad in (torch.tensor([0, 0, 1]), torch.tensor([0, 1, 3]), torch.tensor([0, 1])):

@@ -152,16 +152,17 @@ def test_non_finite_points_are_isolated_and_nobodys_neighbour():
 
 def test_outputs_sit_between_guard_bytes_and_layouts_are_refused_or_copied():
     from itermvs_amd import cloud_filter as CF
+    from itermvs_amd import cloud_grid as CG
     from itermvs_amd import ops
     c = R.census(R.CENSUS[1])
     pts, n, k, cap = c["pts"], len(c["pts"]), c["k"], c["cap"]
     x = dev(pts)
-    grid, xs, keys, perm = CF._sorted_cloud(x, x, 0.03, "test")
+    xs, keys, perm, grid = CG.sort_into_cells(x, 0.03, "test", extent=x)
     pad = 64
     mean = torch.full((n + 2 * pad,), -7.25, device=DEV, dtype=torch.float64)
     flag = torch.full((n + 2 * pad,), 0xA5, device=DEV, dtype=torch.uint8)
     count = torch.full((n + 2 * pad,), -1234567, device=DEV, dtype=torch.int32)
-    ops.cloud_knn_mean(xs, keys, perm, grid, k, cap, CF.max_ring(cap, 0.03), mean[pad:pad + n], flag[pad:pad + n])
+    ops.cloud_knn_mean(xs, keys, perm, grid, k, cap, CG.max_ring(cap, 0.03), mean[pad:pad + n], flag[pad:pad + n])
     ops.cloud_radius_count(xs, keys, perm, grid, 0.05, 9, count[pad:pad + n])
     for buf, fill in ((mean, -7.25), (flag, 0xA5), (count, -1234567)):
         assert bool((buf[:pad] == fill).all()) and bool((buf[pad + n:] == fill).all())
@@ -172,12 +173,12 @@ def test_outputs_sit_between_guard_bytes_and_layouts_are_refused_or_copied():
     flag2 = torch.full((n,), 0xA5, device=DEV, dtype=torch.uint8)
     mean2 = torch.full((n,), -7.25, device=DEV, dtype=torch.float64)
     index = torch.arange(0, n, 3, device=DEV, dtype=torch.int64)
-    ops.cloud_knn_mean(xs, keys, perm, grid, k, cap, CF.max_ring(cap, 0.03), mean2, flag2, index=index)
+    ops.cloud_knn_mean(xs, keys, perm, grid, k, cap, CG.max_ring(cap, 0.03), mean2, flag2, index=index)
     touched = torch.zeros((n,), device=DEV, dtype=torch.bool)
     touched[perm[index]] = True
     assert bool((flag2[~touched] == 0xA5).all()) and torch.equal(flag2[touched], flag[pad:pad + n][touched])
     assert torch.equal(mean2[touched], mean[pad:pad + n][touched]) and bool((mean2[~touched] == -7.25).all())
-    # layouts: the public functions copy like _points does, the entry wrappers refuse
+    # layouts: the public functions copy like cloud_grid.points does, the entry wrappers refuse
     wide = torch.zeros((n, 4), device=DEV, dtype=torch.float32)
     wide[:, :3] = x
     m, iso = CF.knn_mean_distance(wide[:, :3], k, cap)

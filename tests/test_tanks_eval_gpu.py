@@ -11,7 +11,7 @@ import torch
 
 import tanks_eval_reference as R
 from conftest import ROOT
-from itermvs_amd import cloud_register as CR, ops
+from itermvs_amd import cloud_grid as CG, cloud_register as CR, ops
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -131,7 +131,7 @@ def test_nn_index_equals_brute_force(with_T):
     assert 0.28 < unmatched < 0.40, unmatched
     for edge in (max_dist / 8, max_dist, 0.3):                                                     # many rings, one ring, fat cells
         tg = CR.build_target_grid(gpu(t), edge)
-        idx, d2 = ops.cloud_nn_index(gpu(q), T, tg.sorted, tg.keys, tg.perm, tg.grid, max_dist, CR.max_ring(max_dist, edge))
+        idx, d2 = ops.cloud_nn_index(gpu(q), T, tg.sorted, tg.keys, tg.perm, tg.grid, max_dist, CG.max_ring(max_dist, edge))
         assert torch.equal(idx.cpu(), torch.from_numpy(want_idx)), edge
         assert np.array_equal(d2.cpu().numpy().view(np.uint64), want_d2.view(np.uint64)), edge
     if not with_T:
@@ -143,7 +143,7 @@ def test_nn_index_bound_is_exclusive_and_empty_targets():
     q = np.array([[0.375, 0.5, 0.0], [0.375, 0.5, 2.0 ** -20]], dtype=np.float32)                  # exactly 0.625 away, and a hair more
     tg = CR.build_target_grid(gpu(t), 0.25)
     for max_dist, want in ((0.625, [-1, -1]), (0.6250001, [0, 0]), (0.62, [-1, -1])):
-        idx, d2 = ops.cloud_nn_index(gpu(q), np.eye(4), tg.sorted, tg.keys, tg.perm, tg.grid, max_dist, CR.max_ring(max_dist, 0.25))
+        idx, d2 = ops.cloud_nn_index(gpu(q), np.eye(4), tg.sorted, tg.keys, tg.perm, tg.grid, max_dist, CG.max_ring(max_dist, 0.25))
         assert idx.tolist() == want and R.nn_index(q.astype(np.float64), t, max_dist)[0].tolist() == want
         assert d2[0].item() == (0.390625 if want[0] == 0 else float("inf"))
     empty = CR.build_target_grid(torch.zeros((0, 3), device=DEV), 0.25)
