@@ -148,9 +148,16 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--mesh_min_count", type=int, default=2,
                    help="--mesh: views that must have seen a voxel before it takes part in a triangle.  The default asks a second view "
                         "to confirm free or occupied space; a choice, not a measured optimum")
+    p.add_argument("--mesh_min_component", type=int, default=None, metavar="N",
+                   help="--mesh: leave the connected components of the mesh with fewer than N triangles out of <scan>_mesh.ply "
+                        "(floating fragments; found and removed on the GPU before the download).  No default: without this flag and "
+                        "--mesh_component_share every triangle is written, as before")
+    p.add_argument("--mesh_component_share", type=float, default=None, metavar="F",
+                   help="--mesh: leave out the components with fewer than F x the triangles of the largest component, F in [0, 1]: "
+                        "a threshold without a scale.  With --mesh_min_component a component must pass both.  No default")
     p.add_argument("--mesh_budget_gb", type=float, default=16.0,
                    help="--mesh: GPU memory in GiB that the kept fused views (9 bytes per pixel and view), the volume, the extraction "
-                        "workspace and the mesh buffers may take together; a larger request stops with the bytes it needs.  A choice")
+                        "workspace, the mesh buffers and the component filter's labels, counts and workspace may take together; a larger request stops with the bytes it needs.  A choice")
     p.add_argument("--clean_cloud", default=None, choices=["statistical", "radius"],
                    help="--filter: also write <outdir>/<scan>_clean.ply, the scan's cloud without its outliers (floaters: sky pixels, "
                         "specular surfaces, thin structures that pass the masks in a few views); <scan>.ply and every other output "
@@ -310,7 +317,12 @@ def check_ply_normals(args) -> bool:
 
 
 def check_mesh(args) -> bool:
-    """--mesh needs --filter and the GPU point assembly; its numeric flags are checked where the options are built, before any work"""
+    """--mesh needs --filter and the GPU point assembly; its numeric flags are checked where the options are built, before any work.
+    --mesh_min_component and --mesh_component_share need --mesh: an argparse error (usage, exit status 2) without it"""
+    if not getattr(args, "mesh", False):
+        for flag in ("mesh_min_component", "mesh_component_share"):
+            if getattr(args, flag, None) is not None:
+                build_parser().error("--{} needs --mesh (it filters the mesh's connected components)".format(flag))
     if not _check_gpu_assembly_flag(args, "mesh", "--mesh", "the volume is integrated from the fused depth maps that stay on the GPU"):
         return False
     from itermvs_amd import fusion

@@ -868,6 +868,52 @@ int itermvs_tsdf_mesh(const uint32_t* state, int32_t nx, int32_t ny, int32_t nz,
                       uint64_t* totals, uint8_t* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Connected components of an indexed triangle mesh and the compaction of the components worth keeping (eval.py
+ * --mesh_min_component / --mesh_component_share, clean_mesh.py; csrc/mesh_components.hip; no counterpart in the reference; numpy
+ * restatement: tests/mesh_components_reference.py).  Integers only: every output is determined by the inputs bit for bit, whatever
+ * the scheduling.  faces: device [NF][3] int32 vertex indices.  A face is VALID iff all three indices lie in [0, NV); an invalid
+ * face is ignored everywhere (not united, not counted, not emitted), like an out-of-range entry of the COLMAP kernels below.
+ * Degenerate faces (a, a, b) and duplicate faces are valid and count.
+ *
+ * itermvs_mesh_components -- label, face_count: device [NV] int32; totals: device uint64 [3].
+ *   1. Two vertices are connected iff a chain of valid faces links them; sharing ONE vertex index is enough.
+ *   2. label[v] = the smallest vertex index of v's component; a vertex that no valid face references has label[v] = v.
+ *   3. face_count[r] = the number of valid faces whose vertices carry label r, stored where label[r] == r; 0 everywhere else.
+ *   4. totals = the number of components with at least one face | the largest face_count | the number of valid faces.
+ *   A memset of totals and five launches (init, hook, flatten, count, totals; hook and count are skipped for NF == 0): a lock-free
+ *   union-find whose one hooking store is a compare-and-swap at a root that hangs the larger root under the smaller, so a parent only
+ *   ever decreases and every walk and every retry ends by construction; integer atomicMin / atomicCAS / atomicAdd / atomicMax at
+ *   agent scope; no thread waits on another thread's progress, the host is not asked between the launches.
+ *   Validation before any HIP call: ITERMVS_ERR_NULL for NULL label, face_count or totals, and for NULL faces unless NF == 0;
+ *   ITERMVS_ERR_DIMS for NV < 0, NF < 0 and NF > 2^31 - 1 (the int32 limit of csrc/flat_launch.hpp: a face_count never wraps).
+ *   NV == 0 and NF == 0 are legal: totals is written, for NV == 0 nothing else.
+ *
+ * itermvs_mesh_keep -- vertices: device [NV] records of record_bytes (1..64; the mesh's is 15) bytes, unpadded; label, face_count as
+ *   itermvs_mesh_components wrote them for `faces`.
+ *   1. A vertex v is kept iff face_count[label[v]] >= min_faces (>= 1); a vertex that no valid face references therefore goes.
+ *      (A label outside [0, NV) keeps nothing.)
+ *   2. A face is kept iff it is valid and its first vertex is kept (its other two carry the same label).
+ *   3. out_vertices: the kept records, unchanged, in ascending v.  out_faces: the kept faces in ascending order, each index replaced
+ *      by its vertex's rank among the kept vertices.
+ *   Capacities and totals (device uint64 [2] = kept vertices, kept faces) as for itermvs_tsdf_mesh: a vertex or face whose number is
+ *   >= its capacity is not stored, totals holds the true counts all the same, the stored faces hold the true new indices; nothing
+ *   outside out_vertices[0 : record_bytes*vertex_capacity], out_faces[0 : 3*face_capacity], totals and the workspace is written.
+ *   Five launches (mark + per-256 count of the vertices, per-256 count of the faces, one-workgroup scan, vertex scatter, face
+ *   scatter; the face launches are skipped for NF == 0); no atomics, no workgroup waits on another.
+ *   workspace: the *bytes of itermvs_mesh_keep_workspace_bytes(NV, NF, bytes) (8 per 256 vertices and per 256 faces + 5 per vertex,
+ *   rounded up to 8), 8-byte aligned.
+ *   Validation before any HIP call: ITERMVS_ERR_NULL for NULL label, face_count, totals or workspace, NULL vertices unless NV == 0,
+ *   NULL faces unless NF == 0, NULL out_vertices / out_faces with a capacity other than 0; ITERMVS_ERR_DIMS for the sizes as above,
+ *   record_bytes outside 1..64, min_faces < 1, a capacity < 0 and vertex_capacity > 2^31 - 1; ITERMVS_ERR_ALIGN for the workspace.
+ * ------------------------------------------------------------------------------------------ */
+int itermvs_mesh_components(const int32_t* faces, int64_t NF, int32_t NV, int32_t* label, int32_t* face_count, uint64_t* totals,
+                            void* stream);
+int itermvs_mesh_keep_workspace_bytes(int32_t NV, int64_t NF, int64_t* bytes /* host */);
+int itermvs_mesh_keep(const uint8_t* vertices, int32_t NV, int32_t record_bytes, const int32_t* faces, int64_t NF, const int32_t* label,
+                      const int32_t* face_count, int32_t min_faces, uint8_t* out_vertices, int64_t vertex_capacity, int32_t* out_faces,
+                      int64_t face_capacity, uint64_t* totals, uint8_t* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The COLMAP converter's two device stages (csrc/colmap.hip; colmap_input.py of the reference, host side: itermvs_amd/colmap.py).
  * Common inputs (device): the images' observation lists as CSR -- offsets [V+1] int64 ascending, point [offsets[V]] int32 = dense
  *   point index into xyz or -1, in file order (image index = position in images.bin) -- and xyz [P][3] fp64.  An entry outside

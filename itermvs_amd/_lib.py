@@ -219,6 +219,10 @@ PROTOTYPES = {
     "itermvs_tsdf_mesh_workspace_bytes": (C.c_int, [C.c_int32] * 3 + [C.POINTER(C.c_int64)]),
     "itermvs_tsdf_mesh": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.c_double] * 4 + [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                     C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "itermvs_mesh_components": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "itermvs_mesh_keep_workspace_bytes": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
+    "itermvs_mesh_keep": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "itermvs_view_scores": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p,
                                       C.c_void_p]),
     "itermvs_depth_ranges": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

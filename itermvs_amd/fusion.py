@@ -222,7 +222,9 @@ class MeshOptions:
     the ``bounds_quantile`` rule of ``mesh_bounds`` on the emitted cloud, widened by the truncation distance.  voxel: the voxel's
     side; None: the longest side of the (unwidened) bounds / ``resolution``.  trunc_voxels: truncation distance in voxels.
     min_count: views a voxel needs to be valid.  budget_bytes: GPU memory the kept views, the volume, the extraction workspace and
-    the mesh buffers may take together.  batch_views: views per integrate launch.  The defaults are choices, not measured optima."""
+    the mesh buffers may take together.  batch_views: views per integrate launch.  The defaults are choices, not measured optima.
+    min_component (triangles) and component_share (of the largest component's triangles, in [0, 1]): the connected components of the
+    mesh with fewer triangles than ``mesh_min_faces`` makes of the two are left out of the file; both 0: no filter, no kernel."""
     path: str
     bounds: Optional[Sequence[float]] = None
     bounds_quantile: float = 0.01
@@ -232,6 +234,8 @@ class MeshOptions:
     min_count: int = 2
     budget_bytes: int = 16 << 30
     batch_views: int = MESH_INTEGRATE_BATCH
+    min_component: int = 0
+    component_share: float = 0.0
 
 
 def mesh_options(mesh) -> Optional[MeshOptions]:
@@ -257,7 +261,25 @@ def mesh_options(mesh) -> Optional[MeshOptions]:
     if int(m.min_count) < 1 or int(m.batch_views) < 1 or int(m.budget_bytes) < 1:
         raise ValueError(f"mesh: min_count, batch_views and budget_bytes must be at least 1, got {m.min_count}, {m.batch_views}, "
                          f"{m.budget_bytes}")
+    problem = component_problem(m.min_component, m.component_share)
+    if problem:
+        raise ValueError("mesh: " + problem)
     return m
+
+
+def component_problem(min_component, component_share) -> Optional[str]:
+    """what is wrong with the two thresholds of the component filter, or None"""
+    if isinstance(min_component, bool) or not isinstance(min_component, (int, np.integer)) or not 0 <= int(min_component) <= 0x7fffffff:
+        return f"min_component must be a whole number of triangles in [0, 2^31 - 1], got {min_component!r}"
+    if isinstance(component_share, bool) or not isinstance(component_share, (int, float, np.integer, np.floating)) \
+            or not 0.0 <= float(component_share) <= 1.0:
+        return f"component_share must be a number in [0, 1], got {component_share!r}"
+    return None
+
+
+def mesh_min_faces(min_component: int, component_share: float, largest: int) -> int:
+    """the triangles a component needs to stay, given the ``largest`` component's: a share of exactly k triangles asks for k"""
+    return max(1, int(min_component), math.ceil(float(component_share) * int(largest)))
 
 
 def mesh_options_from_args(args, path: str) -> Optional[MeshOptions]:
@@ -268,7 +290,9 @@ def mesh_options_from_args(args, path: str) -> Optional[MeshOptions]:
                                     bounds_quantile=getattr(args, "mesh_bounds_quantile", 0.01), voxel=getattr(args, "mesh_voxel", None),
                                     resolution=getattr(args, "mesh_resolution", 256), trunc_voxels=getattr(args, "mesh_trunc", 3.0),
                                     min_count=getattr(args, "mesh_min_count", 2),
-                                    budget_bytes=int(getattr(args, "mesh_budget_gb", 16.0) * (1 << 30))))
+                                    budget_bytes=int(getattr(args, "mesh_budget_gb", 16.0) * (1 << 30)),
+                                    min_component=getattr(args, "mesh_min_component", None) or 0,
+                                    component_share=getattr(args, "mesh_component_share", None) or 0.0))
 
 
 def mesh_bounds(xyz, quantile: float) -> Tuple[float, ...]:
@@ -356,11 +380,55 @@ def extract_mesh(state: torch.Tensor, plan: dict, min_count: int, budget_bytes: 
     return vertices, faces
 
 
+def keep_mesh_components(vertices: torch.Tensor, faces: torch.Tensor, min_component: int = 0, component_share: float = 0.0,
+                         budget_bytes: int = None, used_bytes: int = 0, info: dict = None, record_bytes: int = ops.MESH_VERTEX_BYTES):
+    """the connected components of a mesh on the GPU (vertex bytes uint8 [nv*record_bytes], faces int32 [nf*3], as ``extract_mesh``
+    returns them) with at least ``mesh_min_faces`` triangles -> (vertices, faces) of the same form, in their order, the faces
+    renumbered.  ``itermvs_mesh_components``, one read of its three totals, then ``itermvs_mesh_keep`` twice like ``extract_mesh``:
+    with capacities 0 for the totals, then into buffers of exactly that size.  The labels, counts, workspace and kept buffers are
+    checked against what the budget has left before they are allocated.  ``info`` receives the counts."""
+    problem = component_problem(min_component, component_share)
+    if problem:
+        raise ValueError("mesh: " + problem)
+    dev, rec = faces.device, int(record_bytes)
+    nv, nf = vertices.numel() // rec, faces.numel() // 3
+    label_bytes, count_bytes, workspace_bytes = 4 * nv, 4 * nv, ops.mesh_keep_workspace_bytes(nv, nf)
+    hint = "lower --mesh_resolution, raise --mesh_voxel or raise --mesh_budget_gb"
+    if budget_bytes is not None and used_bytes + label_bytes + count_bytes + workspace_bytes > budget_bytes:
+        raise ValueError(f"mesh: the component filter of {nv} vertices and {nf} triangles needs {label_bytes} bytes of labels, "
+                         f"{count_bytes} of counts and {workspace_bytes} of workspace on top of {used_bytes}, the budget is "
+                         f"{budget_bytes}; {hint}")
+    label, face_count, totals = ops.mesh_components(faces, nv)
+    components, largest, valid = (int(t) for t in totals.tolist())
+    min_faces = mesh_min_faces(min_component, component_share, largest)
+    workspace = torch.empty(max(workspace_bytes, 8), device=dev, dtype=torch.uint8)
+    kept = torch.zeros(2, device=dev, dtype=torch.int64)
+    args = (vertices, rec, faces, label, face_count, min_faces)
+    ops.mesh_keep(*args, torch.empty(0, device=dev, dtype=torch.uint8), torch.empty(0, device=dev, dtype=torch.int32), kept, workspace)
+    kv, kf = (int(t) for t in kept.tolist())
+    out_bytes = kv * rec + kf * ops.MESH_FACE_BYTES
+    if budget_bytes is not None and used_bytes + label_bytes + count_bytes + workspace_bytes + out_bytes > budget_bytes:
+        raise ValueError(f"mesh: the kept {kv} vertices and {kf} triangles need {out_bytes} bytes on top of {used_bytes} and the "
+                         f"component filter's {label_bytes + count_bytes + workspace_bytes} (labels, counts, workspace), the budget "
+                         f"is {budget_bytes}; {hint}")
+    out_vertices = torch.empty(kv * rec, device=dev, dtype=torch.uint8)
+    out_faces = torch.empty(kf * 3, device=dev, dtype=torch.int32)
+    if kv or kf:
+        ops.mesh_keep(*args, out_vertices, out_faces, kept, workspace)
+    if info is not None:
+        kept_components = int((face_count >= min_faces).sum()) if nv else 0
+        info.update(components=components, largest=largest, min_faces=min_faces, kept_components=kept_components,
+                    valid_faces=valid, vertices_before=nv, faces_before=nf, vertices=kv, faces=kf,
+                    component_bytes=label_bytes + count_bytes + workspace_bytes)
+    return out_vertices, out_faces
+
+
 def write_scan_mesh(mesh: MeshOptions, bounds: Sequence[float], depth: torch.Tensor, mask: torch.Tensor, cams: torch.Tensor,
                     rgb: torch.Tensor, info: dict = None) -> None:
     """the kept views (depth float64 [V,H,W], mask uint8 [V,H,W], cams float32 [V,21] = K | E[:3], rgb uint8 [V,H,W,3], on the GPU, in
     pair.txt order) -> ``mesh.path``: the volume of ``mesh_plan``, ``itermvs_tsdf_integrate`` in batches of ``mesh.batch_views``,
-    ``extract_mesh``, one download"""
+    ``extract_mesh``, ``keep_mesh_components`` when ``mesh.min_component`` or ``mesh.component_share`` is set, one download (of the
+    kept mesh alone)"""
     v, h, w = depth.shape
     kept = v * h * w * MESH_KEPT_BYTES_PER_PIXEL
     plan = mesh_plan(bounds, mesh.voxel, mesh.resolution, mesh.trunc_voxels, widen=mesh.bounds is None,
@@ -370,10 +438,19 @@ def write_scan_mesh(mesh: MeshOptions, bounds: Sequence[float], depth: torch.Ten
         b = min(a + int(mesh.batch_views), v)
         ops.tsdf_integrate(state, plan["dims"], plan["origin"], plan["voxel"], plan["trunc"], depth[a:b], mask[a:b], cams[a:b], rgb[a:b])
     vertices, faces = extract_mesh(state, plan, mesh.min_count, mesh.budget_bytes, plan["need_bytes"])
+    kept_info = {}
+    if mesh.min_component or mesh.component_share:
+        had = vertices.numel() + faces.numel() * 4
+        vertices, faces = keep_mesh_components(vertices, faces, mesh.min_component, mesh.component_share, mesh.budget_bytes,
+                                               plan["need_bytes"] + had, kept_info)
+        if had and not faces.numel():
+            kept_info.update(warning=f"mesh: no component has {kept_info['min_faces']} triangles (the largest has "
+                                     f"{kept_info['largest']}): {mesh.path} is an empty mesh")
     write_ply_mesh(mesh.path, vertices.cpu().numpy(), faces.cpu().numpy())
     if info is not None:
         info.update(plan, bounds=tuple(bounds), vertices=vertices.numel() // ops.MESH_VERTEX_BYTES, faces=faces.numel() // 3,
                     batches=(v + int(mesh.batch_views) - 1) // int(mesh.batch_views))
+        info.update(kept_info)
 
 
 def fuse_scan(pairs: Sequence[Tuple[int, Sequence[int]]], cams, depths, confidences, images, plyfilename: str,

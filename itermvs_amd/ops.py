@@ -1544,6 +1544,68 @@ def tsdf_mesh(state: Tensor, dims: Sequence[int], origin: Sequence[float], voxel
           "itermvs_tsdf_mesh")
 
 
+def mesh_components(faces: Tensor, n_vertices: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """itermvs_mesh_components: ``faces`` int32 [NF,3] (or flat [NF*3]) of a mesh of ``n_vertices`` vertices -> (label int32 [NV] =
+    the smallest vertex index of each vertex's component, face_count int32 [NV] = the valid faces of a component at its label,
+    totals int64 [3] = components with a face, largest face_count, valid faces), all on the GPU; nothing is read back."""
+    what = "mesh_components"
+    _tsdf_tensor(what, "faces", faces, torch.int32)
+    nv = int(n_vertices)
+    if faces.numel() % 3 or nv < 0:
+        raise RuntimeError(f"{what}: faces must hold index triples and n_vertices be >= 0, got {faces.numel()} indices, {nv} vertices")
+    nf = faces.numel() // 3
+    store = torch.empty((2, max(nv, 1)), device=faces.device, dtype=torch.int32)       # an empty tensor has no address, and the
+    label, face_count = store[0, :nv], store[1, :nv]                                   # entry point refuses NULL whatever NV is
+    totals = torch.empty(3, device=faces.device, dtype=torch.int64)
+    check(_lib.load().itermvs_mesh_components(faces.data_ptr() if nf else None, nf, nv, store[0].data_ptr(), store[1].data_ptr(),
+                                              totals.data_ptr(), _stream()), "itermvs_mesh_components")
+    return label, face_count, totals
+
+
+def mesh_keep_workspace_bytes(n_vertices: int, n_faces: int) -> int:
+    n = C.c_int64(0)
+    check(_lib.load().itermvs_mesh_keep_workspace_bytes(int(n_vertices), int(n_faces), C.byref(n)), "itermvs_mesh_keep_workspace_bytes")
+    return int(n.value)
+
+
+def mesh_keep(vertices: Tensor, record_bytes: int, faces: Tensor, label: Tensor, face_count: Tensor, min_faces: int,
+              out_vertices: Tensor, out_faces: Tensor, totals: Tensor, workspace: Optional[Tensor] = None,
+              vertex_capacity: Optional[int] = None, face_capacity: Optional[int] = None) -> None:
+    """itermvs_mesh_keep: the vertices (uint8, ``record_bytes`` each) and faces (int32 triples) of the components with at least
+    ``min_faces`` valid faces -> ``out_vertices``, ``out_faces`` (in their order, faces renumbered) and ``totals`` (int64 [2]: kept
+    vertices, kept faces, whatever the capacities); nothing is read back.  ``label``, ``face_count``: ``mesh_components`` of the same
+    faces.  The capacities default to all of the two buffers; ``workspace``: uint8 scratch of mesh_keep_workspace_bytes, allocated
+    here when not given."""
+    what = "mesh_keep"
+    rec = int(record_bytes)
+    for name, t, dtype in (("vertices", vertices, torch.uint8), ("faces", faces, torch.int32), ("label", label, torch.int32),
+                           ("face_count", face_count, torch.int32), ("out_vertices", out_vertices, torch.uint8),
+                           ("out_faces", out_faces, torch.int32)):
+        _tsdf_tensor(what, name, t, dtype)
+    _tsdf_tensor(what, "totals", totals, torch.int64, (2,))
+    if rec < 1 or vertices.numel() % rec or faces.numel() % 3:
+        raise RuntimeError(f"{what}: {vertices.numel()} vertex bytes are no records of {rec} bytes, or {faces.numel()} indices no triples")
+    nv, nf = vertices.numel() // rec, faces.numel() // 3
+    if label.numel() != nv or face_count.numel() != nv:
+        raise RuntimeError(f"{what}: label and face_count must have one entry per vertex ({nv}), got {label.numel()}, {face_count.numel()}")
+    vcap = out_vertices.numel() // rec if vertex_capacity is None else int(vertex_capacity)
+    fcap = out_faces.numel() // 3 if face_capacity is None else int(face_capacity)
+    if vcap < 0 or vcap * rec > out_vertices.numel() or fcap < 0 or fcap * 3 > out_faces.numel():
+        raise RuntimeError(f"{what}: capacities {vcap} vertices, {fcap} triangles do not fit the buffers "
+                           f"({out_vertices.numel()} bytes, {out_faces.numel()} indices)")
+    need = mesh_keep_workspace_bytes(nv, nf)
+    if workspace is None:
+        workspace = torch.empty(max(need, 8), device=faces.device, dtype=torch.uint8)
+    elif not workspace.is_cuda or workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous():
+        raise RuntimeError(f"{what}: workspace must be a contiguous uint8 CUDA/ROCm tensor of >= {need} bytes")
+    if nv == 0:                                                    # empty tensors have no address: see mesh_components
+        label = face_count = torch.empty(1, device=faces.device, dtype=torch.int32)
+    check(_lib.load().itermvs_mesh_keep(vertices.data_ptr() if nv else None, nv, rec, faces.data_ptr() if nf else None, nf,
+                                        label.data_ptr(), face_count.data_ptr(), int(min_faces),
+                                        out_vertices.data_ptr() if vcap else None, vcap, out_faces.data_ptr() if fcap else None, fcap,
+                                        totals.data_ptr(), workspace.data_ptr(), _stream()), "itermvs_mesh_keep")
+
+
 def _colmap_inputs(what: str, offsets: Tensor, point: Tensor, xyz: Tensor, per_view: Tensor, width: int) -> Tuple[int, int]:
     """shared checks of view_scores / depth_ranges -> (V, P).  ``offsets`` is the one HOST tensor: its values are checked here
     (ascending from offsets[0] >= 0 to offsets[V] <= len(point)), which the kernels rely on for their reads of ``point``."""
