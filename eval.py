@@ -517,8 +517,8 @@ def save_depth_folder(args, dataset, mine, model, dev) -> int:
 def fuse_scans(args) -> int:
     """eval.py:311-325: one point cloud per scan; scans are sharded over the ranks like the reference views"""
     from itermvs_amd import fusion
-    dedupe = check_fuse_dedupe(args)
-    normals = check_ply_normals(args)
+    check_fuse_dedupe(args)
+    check_ply_normals(args)
     check_mesh(args)
     check_geo_consistency(args)
     check_clean_cloud(args)
@@ -530,15 +530,10 @@ def fuse_scans(args) -> int:
     for i in shard.shard_indices(len(scans), rank, world):
         scan = scans[i]
         stats = fusion.filter_depth(os.path.join(args.testpath, scan), os.path.join(args.outdir, scan),
-                                    os.path.join(args.outdir, scan + ".ply"), args.geo_pixel_thres, args.geo_depth_thres,
-                                    args.photo_thres, geo_mask_thres=args.geo_mask_thres, device=dev, img_wh=tuple(args.img_wh),
-                                    points=args.fuse_points,
-                                    save_masks=args.save_masks, dedupe=dedupe, normals=normals,
-                                    normal_edge_thres=getattr(args, "normal_edge_thres", 0.01),
-                                    mesh=fusion.mesh_options_from_args(args, os.path.join(args.outdir, scan + "_mesh.ply")),
-                                    **fusion.consistency_from_args(args))
-        for v, (g, ph, f) in stats.items():
-            print("processing {}, ref-view{:0>2}, geo_mask:{:3f} photo_mask:{:3f} final_mask: {:3f}".format(scan, v, g, ph, f))
+                                    os.path.join(args.outdir, scan + ".ply"), device=dev, img_wh=tuple(args.img_wh),
+                                    points=args.fuse_points, save_masks=args.save_masks,
+                                    **fusion.fuse_keywords_from_args(args, os.path.join(args.outdir, scan + "_mesh.ply")))
+        fusion.print_view_shares(scan, stats)
         clean_scan_cloud(args, scan, dev)
         n += 1
     shard.barrier()

@@ -28,6 +28,16 @@ def read_camera_parameters(filename: str) -> Tuple[np.ndarray, np.ndarray]:
     return intrinsics, extrinsics
 
 
+def read_scaled_camera(scan_folder: str, view: int, sx: float, sy: float) -> Tuple[np.ndarray, np.ndarray]:
+    """``cams_1/{view:0>8}_cam.txt`` with the intrinsics rescaled to the depth maps' size like eval.py:231-232: a python float
+    times a float32 row stays float32.  The files and the memory path of the fusion get byte-identical clouds from this one copy."""
+    k, e = read_camera_parameters(os.path.join(scan_folder, "cams_1/{:0>8}_cam.txt".format(view)))
+    k = k.copy()
+    k[0] *= sx
+    k[1] *= sy
+    return k, e
+
+
 def read_pair_file(filename: str) -> List[Tuple[int, List[int]]]:
     """eval.py:90-100"""
     data = []
@@ -66,7 +76,7 @@ def dynamic_problem(dyn_pixel_step, dyn_depth_step, dyn_n_min, dyn_n_max) -> Opt
 def dynamic_options(consistency: str = "static", dyn_pixel_step: float = ops.DYN_PIXEL_STEP, dyn_depth_step: float = ops.DYN_DEPTH_STEP,
                     dyn_n_min: int = ops.DYN_N_MIN, dyn_n_max: int = ops.DYN_N_MAX) -> Optional[dict]:
     """``consistency`` "static": None (the count against ``geo_mask_thres``); "dynamic": the checked keyword arguments of the
-    level rule for ``ops.fuse_depth_dynamic`` (include/itermvs_hip.h: itermvs_fuse_depth_dynamic)"""
+    level rule for ``fuse_view`` (include/itermvs_hip.h: itermvs_fuse_depth_dynamic)"""
     if consistency not in ("static", "dynamic"):
         raise ValueError(f"consistency must be 'static' or 'dynamic', got {consistency!r}")
     if consistency == "static":
@@ -90,23 +100,49 @@ def consistency_from_args(args) -> dict:
                 dyn_depth_step=given("dyn_depth_step", ops.DYN_DEPTH_STEP), dyn_n_min=levels[0], dyn_n_max=levels[1])
 
 
+def fuse_keywords_from_args(args, mesh_path: str) -> dict:
+    """the fusion flags of eval.py -> the keyword arguments both drivers pass to ``filter_depth`` / ``fuse_scan``: the four
+    thresholds, ``dedupe``, ``normals``, ``normal_edge_thres``, ``mesh`` (written to ``mesh_path``) and the consistency rule"""
+    return dict(geo_pixel_thres=args.geo_pixel_thres, geo_depth_thres=args.geo_depth_thres, photo_thres=args.photo_thres,
+                geo_mask_thres=args.geo_mask_thres, dedupe=bool(getattr(args, "fuse_dedupe", False)),
+                normals=bool(getattr(args, "ply_normals", False)), normal_edge_thres=float(getattr(args, "normal_edge_thres", 0.01)),
+                mesh=mesh_options_from_args(args, mesh_path), **consistency_from_args(args))
+
+
+def print_view_shares(scan: str, stats: Dict[int, Tuple[float, float, float]]) -> None:
+    """the line eval.py:270-272 prints per reference view"""
+    for v, (g, ph, f) in stats.items():
+        print("processing {}, ref-view{:0>2}, geo_mask:{:3f} photo_mask:{:3f} final_mask: {:3f}".format(scan, v, g, ph, f))
+
+
+def fuse_view(depth_ref, conf_ref, depth_src: Sequence, mats, geo_pixel_thres, geo_depth_thres, photo_thres, geo_mask_thres,
+              dyn: Optional[dict] = None, claims: Optional[tuple] = None):
+    """one reference view on the GPU through the entry point its options ask for, the only place that chooses: ``dyn`` (what
+    ``dynamic_options`` returns) -> ``itermvs_fuse_depth_dynamic``, which takes no ``geo_mask_thres``, with or without ``claims`` =
+    (claimed_ref, claimed_src); static with claims -> ``itermvs_fuse_depth_claim``; else ``itermvs_fuse_depth``.  -> that call's tuple"""
+    maps, thres = (depth_ref, conf_ref, depth_src, mats), (geo_pixel_thres, geo_depth_thres, photo_thres)
+    if dyn is not None:
+        return ops.fuse_depth_dynamic(*maps, *(claims or (None, None)), *thres, **dyn)
+    if claims is not None:
+        return ops.fuse_depth_claim(*maps, *claims, *thres, geo_mask_thres)
+    return ops.fuse_depth(*maps, *thres, geo_mask_thres)
+
+
 def fuse_reference_view(depth_ref, conf_ref, k_ref, e_ref, src_depths: Sequence, src_ks: Sequence, src_es: Sequence,
                         geo_pixel_thres=1.0, geo_depth_thres=0.01, photo_thres=0.3, geo_mask_thres=3, device="cuda",
                         consistency="static", dyn_pixel_step=ops.DYN_PIXEL_STEP, dyn_depth_step=ops.DYN_DEPTH_STEP,
                         dyn_n_min=ops.DYN_N_MIN, dyn_n_max=ops.DYN_N_MAX):
     """eval.py:238-269 for one reference view (numpy or torch inputs) -> torch tensors
     (depth_est_averaged float64, photo_mask, geo_mask, final_mask uint8, geo_mask_sum int32).  ``consistency="dynamic"``: the
-    geometric mask is the level rule of ``ops.fuse_depth_dynamic`` with the four ``dyn_*`` parameters, ``geo_mask_thres`` is not
+    geometric mask is the level rule of ``itermvs_fuse_depth_dynamic`` with the four ``dyn_*`` parameters, ``geo_mask_thres`` is not
     used and the accepting level map (uint8) is returned as a sixth tensor."""
     dev = torch.device(device)
     dyn = dynamic_options(consistency, dyn_pixel_step, dyn_depth_step, dyn_n_min, dyn_n_max)
     as_t = lambda a: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dev, torch.float32)
     mats = np.stack([pair_matrices(np.asarray(k_ref), np.asarray(e_ref), np.asarray(k), np.asarray(e))
                      for k, e in zip(src_ks, src_es)])
-    maps = (as_t(depth_ref), as_t(conf_ref), [as_t(d) for d in src_depths], torch.from_numpy(mats).to(dev))
-    if dyn is not None:
-        return ops.fuse_depth_dynamic(*maps, None, None, geo_pixel_thres, geo_depth_thres, photo_thres, **dyn)
-    return ops.fuse_depth(*maps, geo_pixel_thres, geo_depth_thres, photo_thres, geo_mask_thres)
+    return fuse_view(as_t(depth_ref), as_t(conf_ref), [as_t(d) for d in src_depths], torch.from_numpy(mats).to(dev),
+                     geo_pixel_thres, geo_depth_thres, photo_thres, geo_mask_thres, dyn)
 
 
 def ply_header(n: int, normals: bool = False) -> bytes:
@@ -365,18 +401,30 @@ def extract_mesh(state: torch.Tensor, plan: dict, min_count: int, budget_bytes: 
     args = (state, plan["dims"], plan["origin"], plan["voxel"], int(min_count))
     totals = torch.zeros(2, device=dev, dtype=torch.int64)
     workspace = torch.empty(ops.tsdf_mesh_workspace_bytes(plan["dims"]), device=dev, dtype=torch.uint8)
-    ops.tsdf_mesh(*args, torch.empty(0, device=dev, dtype=torch.uint8), torch.empty(0, device=dev, dtype=torch.int32), totals, workspace)
+
+    def check(nv, nf, out_bytes):
+        if nv > 0x7fffffff:
+            raise ValueError(f"mesh: {nv} vertices do not fit the int32 indices of a PLY face; lower --mesh_resolution or raise --mesh_voxel")
+        if budget_bytes is not None and used_bytes + out_bytes > budget_bytes:
+            raise ValueError(f"mesh: {nv} vertices and {nf} triangles need {out_bytes} bytes on top of {used_bytes}, the budget is "
+                             f"{budget_bytes}; lower --mesh_resolution, raise --mesh_voxel or raise --mesh_budget_gb")
+
+    return _count_then_fill(lambda v, f: ops.tsdf_mesh(*args, v, f, totals, workspace), totals, ops.MESH_VERTEX_BYTES, check)
+
+
+def _count_then_fill(launch, totals: torch.Tensor, vertex_bytes: int, check):
+    """the two runs of a kernel that writes a mesh of unknown size: ``launch(vertices, faces)`` with capacities 0 leaves the vertex
+    and triangle totals in ``totals`` (int64 [2], on the GPU); they are read, ``check(vertices, triangles, output bytes)`` raises what
+    the caller refuses, the buffers are allocated at exactly that size and, unless both are empty, ``launch`` fills them.
+    -> (vertex bytes uint8 [nv*vertex_bytes], faces int32 [nf*3])"""
+    dev = totals.device
+    launch(torch.empty(0, device=dev, dtype=torch.uint8), torch.empty(0, device=dev, dtype=torch.int32))
     nv, nf = (int(t) for t in totals.tolist())
-    out_bytes = nv * ops.MESH_VERTEX_BYTES + nf * ops.MESH_FACE_BYTES
-    if nv > 0x7fffffff:
-        raise ValueError(f"mesh: {nv} vertices do not fit the int32 indices of a PLY face; lower --mesh_resolution or raise --mesh_voxel")
-    if budget_bytes is not None and used_bytes + out_bytes > budget_bytes:
-        raise ValueError(f"mesh: {nv} vertices and {nf} triangles need {out_bytes} bytes on top of {used_bytes}, the budget is "
-                         f"{budget_bytes}; lower --mesh_resolution, raise --mesh_voxel or raise --mesh_budget_gb")
-    vertices = torch.empty(nv * ops.MESH_VERTEX_BYTES, device=dev, dtype=torch.uint8)
+    check(nv, nf, nv * vertex_bytes + nf * ops.MESH_FACE_BYTES)
+    vertices = torch.empty(nv * vertex_bytes, device=dev, dtype=torch.uint8)
     faces = torch.empty(nf * 3, device=dev, dtype=torch.int32)
     if nv or nf:
-        ops.tsdf_mesh(*args, vertices, faces, totals, workspace)
+        launch(vertices, faces)
     return vertices, faces
 
 
@@ -404,22 +452,19 @@ def keep_mesh_components(vertices: torch.Tensor, faces: torch.Tensor, min_compon
     workspace = torch.empty(max(workspace_bytes, 8), device=dev, dtype=torch.uint8)
     kept = torch.zeros(2, device=dev, dtype=torch.int64)
     args = (vertices, rec, faces, label, face_count, min_faces)
-    ops.mesh_keep(*args, torch.empty(0, device=dev, dtype=torch.uint8), torch.empty(0, device=dev, dtype=torch.int32), kept, workspace)
-    kv, kf = (int(t) for t in kept.tolist())
-    out_bytes = kv * rec + kf * ops.MESH_FACE_BYTES
-    if budget_bytes is not None and used_bytes + label_bytes + count_bytes + workspace_bytes + out_bytes > budget_bytes:
-        raise ValueError(f"mesh: the kept {kv} vertices and {kf} triangles need {out_bytes} bytes on top of {used_bytes} and the "
-                         f"component filter's {label_bytes + count_bytes + workspace_bytes} (labels, counts, workspace), the budget "
-                         f"is {budget_bytes}; {hint}")
-    out_vertices = torch.empty(kv * rec, device=dev, dtype=torch.uint8)
-    out_faces = torch.empty(kf * 3, device=dev, dtype=torch.int32)
-    if kv or kf:
-        ops.mesh_keep(*args, out_vertices, out_faces, kept, workspace)
+
+    def check(kv, kf, out_bytes):
+        if budget_bytes is not None and used_bytes + label_bytes + count_bytes + workspace_bytes + out_bytes > budget_bytes:
+            raise ValueError(f"mesh: the kept {kv} vertices and {kf} triangles need {out_bytes} bytes on top of {used_bytes} and the "
+                             f"component filter's {label_bytes + count_bytes + workspace_bytes} (labels, counts, workspace), the budget "
+                             f"is {budget_bytes}; {hint}")
+
+    out_vertices, out_faces = _count_then_fill(lambda v, f: ops.mesh_keep(*args, v, f, kept, workspace), kept, rec, check)
     if info is not None:
         kept_components = int((face_count >= min_faces).sum()) if nv else 0
         info.update(components=components, largest=largest, min_faces=min_faces, kept_components=kept_components,
-                    valid_faces=valid, vertices_before=nv, faces_before=nf, vertices=kv, faces=kf,
-                    component_bytes=label_bytes + count_bytes + workspace_bytes)
+                    valid_faces=valid, vertices_before=nv, faces_before=nf, vertices=out_vertices.numel() // rec,
+                    faces=out_faces.numel() // 3, component_bytes=label_bytes + count_bytes + workspace_bytes)
     return out_vertices, out_faces
 
 
@@ -451,6 +496,156 @@ def write_scan_mesh(mesh: MeshOptions, bounds: Sequence[float], depth: torch.Ten
         info.update(plan, bounds=tuple(bounds), vertices=vertices.numel() // ops.MESH_VERTEX_BYTES, faces=faces.numel() // 3,
                     batches=(v + int(mesh.batch_views) - 1) // int(mesh.batch_views))
         info.update(kept_info)
+
+
+class _DeviceScan:
+    """a scan on the GPU, built once per ``fuse_scan``: depth[view] float32 [H,W] (every map is uploaded once), conf[i] and rgb[i] of
+    the i-th reference view, the pair blocks of all views in ``mats`` (view i's are mats[first_mat[i]:first_mat[i + 1]]), the ``cam``
+    rows inv(K) | inv(E)[:3] of eval.py:291-294 and, with ``dedupe``, one zeroed uint8 claim map per view"""
+
+    def __init__(self, pairs, cams, depths, confidences, images, dev, dedupe: bool):
+        as_t = lambda a, dt: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dev, dt).contiguous()  # noqa: E731
+        f32 = lambda m: np.asarray(m, np.float32)                      # noqa: E731
+        self.pairs, self.depth = pairs, {}
+        for ref, srcs in pairs:
+            for v in (ref, *srcs):
+                if v not in self.depth:
+                    self.depth[v] = as_t(depths[v], torch.float32)
+        self.h, self.w = h, w = self.depth[pairs[0][0]].shape if pairs else (1, 1)
+        self.claimed = {v: torch.zeros((h, w), device=dev, dtype=torch.uint8) for v in self.depth} if dedupe else None
+        self.conf = [as_t(confidences[ref], torch.float32) for ref, _ in pairs]
+        self.rgb = [as_t(images[ref], torch.uint8) for ref, _ in pairs]
+        for (ref, _), t in zip(pairs, self.rgb):
+            if tuple(t.shape) != (h, w, 3):
+                raise ValueError(f"view {ref}: image is {tuple(t.shape[:2])}, depth map is {(h, w)}")
+        mats, cam = [], []
+        for ref, srcs in pairs:
+            k_ref, e_ref = f32(cams[ref][0]), f32(cams[ref][1])
+            mats.append(np.stack([pair_matrices(k_ref, e_ref, f32(cams[v][0]), f32(cams[v][1])) for v in srcs]))
+            cam.append(np.concatenate([np.linalg.inv(k_ref).reshape(-1), np.linalg.inv(e_ref)[:3].reshape(-1)]))
+        self.first_mat = np.cumsum([0] + [len(m) for m in mats])
+        self.mats = torch.from_numpy(np.concatenate(mats)).to(dev) if pairs else None
+        self.cam = torch.from_numpy(np.stack(cam).astype(np.float32)).to(dev) if pairs else None
+
+    def inputs(self, i: int) -> tuple:
+        """(depth_ref, conf_ref, [depth_src], mats) of the i-th reference view"""
+        ref, srcs = self.pairs[i]
+        return self.depth[ref], self.conf[i], [self.depth[v] for v in srcs], self.mats[self.first_mat[i]:self.first_mat[i + 1]]
+
+    def claims(self, i: int) -> Optional[tuple]:
+        """(claimed_ref, [claimed_src]) of the i-th reference view, None without ``dedupe``"""
+        ref, srcs = self.pairs[i]
+        return (self.claimed[ref], [self.claimed[v] for v in srcs]) if self.claimed is not None else None
+
+
+class _RecordBuffer:
+    """where the views of a group leave their vertices and counts, allocated once per scan: ``records`` for ``capacity`` vertices (the
+    largest group's worst case unless ``group_capacity`` is given), the ``cursor``, the per-view ``counts``, the emit kernels'
+    ``workspace`` and the pinned ``host`` rows the counts land in (last row: the cursor)"""
+
+    def __init__(self, scan: _DeviceScan, rec: int, groups, group_capacity: Optional[int], records_budget: int, dev):
+        n, h, w = len(scan.pairs), scan.h, scan.w
+        self.scan, self.records_budget = scan, records_budget
+        self.capacity = max((b - a) * h * w for a, b in groups) if group_capacity is None and groups else int(group_capacity or 0)
+        self.records = torch.empty(self.capacity * rec, device=dev, dtype=torch.uint8)
+        self.cursor = torch.zeros(1, device=dev, dtype=torch.int64)
+        self.counts = torch.zeros((max(n, 1), 4), device=dev, dtype=torch.int64)
+        self.workspace = torch.empty(ops.fuse_points_workspace_bytes(h, w), device=dev, dtype=torch.uint8)
+        self.host = torch.empty((n + 1, 4), dtype=torch.int64, pin_memory=True)
+
+    def enqueue_landing(self, a: int, b: int) -> None:
+        self.host[a:b].copy_(self.counts[a:b], non_blocking=True)
+        self.host[-1, :1].copy_(self.cursor, non_blocking=True)
+
+    def landed(self, a: int, b: int, stats: dict) -> int:
+        """after the group's synchronisation: stats[ref_view] = (geo, photo, final mask share) of views a..b-1 -> vertices emitted"""
+        n, pixels = int(self.host[-1, 0]), float(self.scan.h * self.scan.w)
+        if n > self.capacity:
+            raise RuntimeError(f"fuse_scan: reference views {a}..{b - 1} emit {n} vertices, the records buffer holds "
+                               f"{self.capacity} (records_budget {self.records_budget} bytes); nothing was written past it")
+        for i in range(a, b):
+            ph, g, fin = (int(c) / pixels for c in self.host[i, :3])
+            stats[self.scan.pairs[i][0]] = (g, ph, fin)
+        return n
+
+
+class _PlyAppender:
+    """the header-last rule of the cloud's file ``f``: the vertex total is known only with the last group, so the groups before it
+    are spooled as host copies; the last one writes the header, the spooled parts and streams its own records through ``download``"""
+
+    def __init__(self, f, normals: bool, seconds: Dict[str, float], download):
+        self.f, self.normals, self.seconds, self.download = f, normals, seconds, download
+        self.spooled, self.vertices, self.chunks, self.headed = [], 0, 0, False
+
+    def append(self, records, n: int, rec: int, last: bool) -> None:
+        self.vertices += n
+        if not last:
+            self.chunks += self.download(records, n * rec, lambda part: self.spooled.append(part.copy()), self.seconds)
+            return
+        t0 = time.perf_counter()
+        self.f.write(ply_header(self.vertices, self.normals))
+        for part in self.spooled:
+            self.f.write(part)
+        self.seconds["file_write"] += time.perf_counter() - t0
+        self.headed = True
+        self.chunks += self.download(records, n * rec, self.f.write, self.seconds)
+
+
+@contextlib.contextmanager
+def _open_cloud(filename: str, normals: bool, seconds: Dict[str, float], download=_download):
+    """-> the ``_PlyAppender`` of ``filename``; a scan without groups gets the empty header, a raise inside removes the file"""
+    with _remove_on_error(filename), open(filename, "wb") as f:
+        ply = _PlyAppender(f, normals, seconds, download)
+        yield ply
+        if not ply.headed:
+            f.write(ply_header(0, normals))
+
+
+class _MeshKeeper:
+    """what ``fuse_scan(mesh=...)`` holds on the GPU while the cloud is assembled: every reference view's ``depth_avg`` and
+    ``photo & geo``, the colours as one tensor (``scan.rgb`` becomes its views: the emit kernels read the same memory) and, for the
+    default bounds, the emitted coordinates of every group.  The kept views are checked against the budget before they are allocated."""
+
+    def __init__(self, mesh: MeshOptions, scan: _DeviceScan, dev):
+        self.mesh, self.pairs, self.cloud_xyz = mesh, scan.pairs, []
+        n, h, w = len(scan.pairs), scan.h, scan.w
+        if not n:
+            return
+        kept_bytes = n * h * w * MESH_KEPT_BYTES_PER_PIXEL
+        if kept_bytes > mesh.budget_bytes:
+            raise ValueError(f"mesh: keeping {n} fused {w}x{h} views on the GPU takes {kept_bytes} bytes, the budget is "
+                             f"{mesh.budget_bytes} (mesh budget_bytes)")
+        self.depth = torch.empty((n, h, w), device=dev, dtype=torch.float64)
+        self.mask = torch.empty((n, h, w), device=dev, dtype=torch.uint8)
+        self.rgb = torch.stack(scan.rgb)
+        scan.rgb = list(self.rgb)
+
+    def keep_view(self, i: int, avg, photo, geo) -> None:
+        self.depth[i].copy_(avg)
+        self.mask[i].copy_((photo != 0) & (geo != 0))
+
+    def note_group(self, records, n: int, rec: int) -> None:
+        if self.mesh.bounds is None and n:
+            self.cloud_xyz.append(records[:n * rec].view(n, rec)[:, :12].contiguous().view(torch.float32))
+
+    def finish(self, cams, dev) -> dict:
+        """after the last group: the bounds (given, or ``mesh_bounds`` of the emitted cloud) and ``write_scan_mesh``; a scan without
+        reference views gets the empty mesh file.  -> the mesh's ``info``"""
+        info = {}
+        if not self.pairs:
+            write_ply_mesh(self.mesh.path, np.zeros(0, MESH_VERTEX), np.zeros((0, 3), np.int32))
+            return info
+        bounds = self.mesh.bounds
+        if bounds is None:
+            if not self.cloud_xyz:
+                raise ValueError("mesh: the cloud is empty, there is nothing to take the default bounds from (give bounds)")
+            bounds = mesh_bounds(torch.cat(self.cloud_xyz), self.mesh.bounds_quantile)
+        self.cloud_xyz = None
+        f32 = lambda m: np.asarray(m, np.float32)                      # noqa: E731
+        kcam = np.stack([np.concatenate([f32(cams[ref][0]).reshape(-1), f32(cams[ref][1])[:3].reshape(-1)])
+                         for ref, _ in self.pairs]).astype(np.float32)
+        write_scan_mesh(self.mesh, bounds, self.depth, self.mask, torch.from_numpy(kcam).to(dev), self.rgb, info=info)
+        return info
 
 
 def fuse_scan(pairs: Sequence[Tuple[int, Sequence[int]]], cams, depths, confidences, images, plyfilename: str,
@@ -491,131 +686,56 @@ def fuse_scan(pairs: Sequence[Tuple[int, Sequence[int]]], cams, depths, confiden
     dev = torch.device(device)
     mesh = mesh_options(mesh)
     dyn = dynamic_options(consistency, dyn_pixel_step, dyn_depth_step, dyn_n_min, dyn_n_max)
-    clock = time.perf_counter
-    seconds = {"upload": 0.0, "enqueue": 0.0, "gpu_wait": 0.0, "download_wait": 0.0, "file_write": 0.0, "mask_write": 0.0}
-    n_sync = n_chunks = 0
+    thres = (geo_pixel_thres, geo_depth_thres, photo_thres, geo_mask_thres)
     rec = ops.POINT_NORMAL_RECORD_BYTES if normals else ops.POINT_RECORD_BYTES
     emit = ops.fuse_points_normals if normals else ops.fuse_points
     emit_options = {"edge_thres": normal_edge_thres} if normals else {}
+    clock = time.perf_counter
+    seconds = {"upload": 0.0, "enqueue": 0.0, "gpu_wait": 0.0, "download_wait": 0.0, "file_write": 0.0, "mask_write": 0.0}
+    stats, n_sync, mesh_info = {}, 0, None
     with torch.cuda.device(dev):
         t0 = clock()
-        as_t = lambda a, dt: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dev, dt).contiguous()  # noqa: E731
-        on_dev = {}
-        for ref, srcs in pairs:                                        # every map is uploaded once
-            for v in (ref, *srcs):
-                if v not in on_dev:
-                    on_dev[v] = as_t(depths[v], torch.float32)
-        h, w = on_dev[pairs[0][0]].shape if pairs else (1, 1)
-        claimed = {v: torch.zeros((h, w), device=dev, dtype=torch.uint8) for v in on_dev} if dedupe else None
-        conf = [as_t(confidences[ref], torch.float32) for ref, _ in pairs]
-        rgb = [as_t(images[ref], torch.uint8) for ref, _ in pairs]
-        for ref, t in zip((p[0] for p in pairs), rgb):
-            if tuple(t.shape) != (h, w, 3):
-                raise ValueError(f"view {ref}: image is {tuple(t.shape[:2])}, depth map is {(h, w)}")
-        f32 = lambda m: np.asarray(m, np.float32)                      # noqa: E731
-        mats, cam = [], []
-        for ref, srcs in pairs:
-            k_ref, e_ref = f32(cams[ref][0]), f32(cams[ref][1])
-            mats.append(np.stack([pair_matrices(k_ref, e_ref, f32(cams[v][0]), f32(cams[v][1])) for v in srcs]))
-            cam.append(np.concatenate([np.linalg.inv(k_ref).reshape(-1), np.linalg.inv(e_ref)[:3].reshape(-1)]))   # eval.py:291-294
-        first_mat = np.cumsum([0] + [len(m) for m in mats])
-        mats = torch.from_numpy(np.concatenate(mats)).to(dev) if pairs else None
-        cam = torch.from_numpy(np.stack(cam).astype(np.float32)).to(dev) if pairs else None
-        if mesh is not None and pairs:
-            kept_bytes = len(pairs) * h * w * MESH_KEPT_BYTES_PER_PIXEL
-            if kept_bytes > mesh.budget_bytes:
-                raise ValueError(f"mesh: keeping {len(pairs)} fused {w}x{h} views on the GPU takes {kept_bytes} bytes, the budget is "
-                                 f"{mesh.budget_bytes} (mesh budget_bytes)")
-            keep_depth = torch.empty((len(pairs), h, w), device=dev, dtype=torch.float64)
-            keep_mask = torch.empty((len(pairs), h, w), device=dev, dtype=torch.uint8)
-            rgb_all = torch.stack(rgb)
-            rgb = list(rgb_all)                                        # the views the emit kernels read, now of one tensor
-            cloud_xyz = []
-        groups = group_views(len(pairs), h, w, records_budget, rec)
-        capacity = max((b - a) * h * w for a, b in groups) if group_capacity is None and groups else int(group_capacity or 0)
-        records = torch.empty(capacity * rec, device=dev, dtype=torch.uint8)
-        cursor = torch.zeros(1, device=dev, dtype=torch.int64)
-        counts = torch.zeros((max(len(pairs), 1), 4), device=dev, dtype=torch.int64)
-        workspace = torch.empty(ops.fuse_points_workspace_bytes(h, w), device=dev, dtype=torch.uint8)
-        host = torch.empty((len(pairs) + 1, 4), dtype=torch.int64, pin_memory=True)    # the counts' landing place; last row: cursor
+        scan = _DeviceScan(pairs, cams, depths, confidences, images, dev, dedupe)
+        keeper = _MeshKeeper(mesh, scan, dev) if mesh is not None else None
+        groups = group_views(len(pairs), scan.h, scan.w, records_budget, rec)
+        out = _RecordBuffer(scan, rec, groups, group_capacity, records_budget, dev)
         stream = torch.cuda.current_stream()
         seconds["upload"] = clock() - t0
-
-        stats, spooled, n_vertices = {}, [], 0
-        with _remove_on_error(plyfilename), open(plyfilename, "wb") as f:
+        with _open_cloud(plyfilename, normals, seconds) as ply:
             for a, b in groups:
                 t0 = clock()
-                cursor.zero_()
+                out.cursor.zero_()
                 masks = []
-                for i in range(a, b):
-                    ref, srcs = pairs[i]
-                    maps = (on_dev[ref], conf[i], [on_dev[v] for v in srcs], mats[first_mat[i]:first_mat[i + 1]])
-                    thres = (geo_pixel_thres, geo_depth_thres, photo_thres, geo_mask_thres)
-                    if dyn is not None:
-                        claims = (claimed[ref], [claimed[v] for v in srcs]) if dedupe else (None, None)
-                        avg, photo, geo, final, _, _ = ops.fuse_depth_dynamic(*maps, *claims, *thres[:3], **dyn)
-                    elif dedupe:
-                        avg, photo, geo, final, _ = ops.fuse_depth_claim(*maps, claimed[ref], [claimed[v] for v in srcs], *thres)
-                    else:
-                        avg, photo, geo, final, _ = ops.fuse_depth(*maps, *thres)
-                    emit(avg, final, cam[i], rgb[i], records, cursor, counts, i, photo, geo, capacity, workspace, **emit_options)
+                for i in range(a, b):                                  # per view: the fuse launch, the emit launch, the mesh copies
+                    avg, photo, geo, final = fuse_view(*scan.inputs(i), *thres, dyn, scan.claims(i))[:4]
+                    emit(avg, final, scan.cam[i], scan.rgb[i], out.records, out.cursor, out.counts, i, photo, geo, out.capacity,
+                         out.workspace, **emit_options)
                     if mask_folder is not None:
-                        masks.append((ref, photo, geo, final))
-                    if mesh is not None:
-                        keep_depth[i].copy_(avg)
-                        keep_mask[i].copy_((photo != 0) & (geo != 0))
-                host[a:b].copy_(counts[a:b], non_blocking=True)
-                host[-1, :1].copy_(cursor, non_blocking=True)
+                        masks.append((pairs[i][0], photo, geo, final))
+                    if keeper is not None:
+                        keeper.keep_view(i, avg, photo, geo)
+                out.enqueue_landing(a, b)
                 t1 = clock()
                 stream.synchronize()                                   # the group's only synchronisation
                 n_sync += 1
                 t2 = clock()
                 seconds["enqueue"] += t1 - t0
                 seconds["gpu_wait"] += t2 - t1
-                n = int(host[-1, 0])
-                if n > capacity:
-                    raise RuntimeError(f"fuse_scan: reference views {a}..{b - 1} emit {n} vertices, the records buffer holds "
-                                       f"{capacity} (records_budget {records_budget} bytes); nothing was written past it")
-                for i in range(a, b):
-                    ph, g, fin = (int(c) / float(h * w) for c in host[i, :3])
-                    stats[pairs[i][0]] = (g, ph, fin)
-                n_vertices += n
-                if mesh is not None and mesh.bounds is None and n:
-                    cloud_xyz.append(records[:n * rec].view(n, rec)[:, :12].contiguous().view(torch.float32))
-                if b == len(pairs):                                    # the total is known: header, earlier groups, then stream
-                    t3 = clock()
-                    f.write(ply_header(n_vertices, normals))
-                    for part in spooled:
-                        f.write(part)
-                    seconds["file_write"] += clock() - t3
-                    n_chunks += _download(records, n * rec, f.write, seconds)
-                else:
-                    n_chunks += _download(records, n * rec, lambda part: spooled.append(part.copy()), seconds)
+                n = out.landed(a, b, stats)
+                if keeper is not None:
+                    keeper.note_group(out.records, n, rec)
+                ply.append(out.records, n, rec, last=b == len(pairs))
                 t3 = clock()
                 for ref, photo, geo, final in masks:
                     _save_view_masks(mask_folder, ref, photo, geo, final)
                 seconds["mask_write"] += clock() - t3
-            if not groups:
-                f.write(ply_header(0, normals))
-        if mesh is not None:
-            mesh_info = {}
-            if pairs:
-                bounds = mesh.bounds
-                if bounds is None:
-                    if not cloud_xyz:
-                        raise ValueError("mesh: the cloud is empty, there is nothing to take the default bounds from (give bounds)")
-                    bounds = mesh_bounds(torch.cat(cloud_xyz), mesh.bounds_quantile)
-                del cloud_xyz
-                kcam = np.stack([np.concatenate([f32(cams[ref][0]).reshape(-1), f32(cams[ref][1])[:3].reshape(-1)])
-                                 for ref, _ in pairs]).astype(np.float32)
-                write_scan_mesh(mesh, bounds, keep_depth, keep_mask, torch.from_numpy(kcam).to(dev), rgb_all, info=mesh_info)
-            else:
-                write_ply_mesh(mesh.path, np.zeros(0, MESH_VERTEX), np.zeros((0, 3), np.int32))
+        if keeper is not None:
+            mesh_info = keeper.finish(cams, dev)
     if info is not None:
         if mesh is not None:
             info.update(mesh=mesh_info)
-        info.update(groups=groups, synchronisations=n_sync, downloads=len(groups), download_chunks=n_chunks,
-                    vertices=n_vertices, capacity=capacity, seconds=seconds, dedupe=bool(dedupe),
+        info.update(groups=groups, synchronisations=n_sync, downloads=len(groups), download_chunks=ply.chunks,
+                    vertices=ply.vertices, capacity=out.capacity, seconds=seconds, dedupe=bool(dedupe),
                     normals=bool(normals), record_bytes=rec, consistency=consistency)
     return stats
 
@@ -650,15 +770,13 @@ def filter_depth(scan_folder: str, out_folder: str, plyfilename: str, geo_pixel_
     rule = dict(consistency=consistency, dyn_pixel_step=dyn_pixel_step, dyn_depth_step=dyn_depth_step, dyn_n_min=dyn_n_min,
                 dyn_n_max=dyn_n_max)
     dynamic_options(**rule)
-    if dedupe and points != "device":
-        raise ValueError("filter_depth: dedupe=True needs points='device' (the claim maps live on the GPU between the reference "
-                         f"views), got points={points!r}")
-    if normals and points != "device":
-        raise ValueError("filter_depth: normals=True needs points='device' (the normals are computed from the fused depth map on "
-                         f"the GPU while the vertices are emitted), got points={points!r}")
-    if mesh is not None and points != "device":
-        raise ValueError("filter_depth: mesh needs points='device' (the volume is integrated from the fused depth maps that stay on "
-                         f"the GPU), got points={points!r}")
+    for asked, reason in ((dedupe, "dedupe=True needs points='device' (the claim maps live on the GPU between the reference views)"),
+                          (normals, "normals=True needs points='device' (the normals are computed from the fused depth map on the GPU "
+                                    "while the vertices are emitted)"),
+                          (mesh is not None, "mesh needs points='device' (the volume is integrated from the fused depth maps that stay "
+                                             "on the GPU)")):
+        if asked and points != "device":
+            raise ValueError(f"filter_depth: {reason}, got points={points!r}")
     pairs = read_pair_file(os.path.join(scan_folder, "pair.txt"))
     mask_folder = os.path.join(out_folder, "mask") if save_masks else None
     if img_wh is None and images is None and intrinsics_scale is None:
@@ -683,12 +801,7 @@ def filter_depth(scan_folder: str, out_folder: str, plyfilename: str, geo_pixel_
 
     def cam(v, want_pixels=False):
         if v not in cams or (want_pixels and img_wh is not None and v not in pixels):
-            k, e = read_camera_parameters(os.path.join(scan_folder, "cams_1/{:0>8}_cam.txt".format(v)))
-            sx, sy = scale_of(v, want_pixels)
-            k = k.copy()
-            k[0] *= sx           # python float * float32 row -> float32, like eval.py:231-232
-            k[1] *= sy
-            cams[v] = (k, e)
+            cams[v] = read_scaled_camera(scan_folder, v, *scale_of(v, want_pixels))
         return cams[v]
 
     def depth(v):
@@ -724,24 +837,28 @@ def filter_depth(scan_folder: str, out_folder: str, plyfilename: str, geo_pixel_
         avg, photo, geo, final = fuse_reference_view(depth(ref_view), conf, k_ref, e_ref, [depth(v) for v in src_views],
                                                      [cam(v)[0] for v in src_views], [cam(v)[1] for v in src_views],
                                                      geo_pixel_thres, geo_depth_thres, photo_thres, geo_mask_thres, device, **rule)[:4]
-        final_np = final.cpu().numpy().astype(bool)
         if save_masks:
             _save_view_masks(mask_folder, ref_view, photo, geo, final)
         stats[ref_view] = (float(geo.float().mean()), float(photo.float().mean()), float(final.float().mean()))
-        h, w = final_np.shape
-        x, y = np.meshgrid(np.arange(0, w), np.arange(0, h))
-        x, y, d = x[final_np], y[final_np], avg.cpu().numpy()[final_np]
-        xyz_ref = np.matmul(np.linalg.inv(k_ref), np.vstack((x, y, np.ones_like(x))) * d)          # eval.py:291-292
-        xyz_world = np.matmul(np.linalg.inv(e_ref), np.vstack((xyz_ref, np.ones_like(x))))[:3]    # eval.py:293-294
-        vertexs.append(xyz_world.transpose((1, 0)))
-        if images is not None:
-            img = images[ref_view]
-        elif ref_view in pixels:
-            img = pixels.pop(ref_view)
-        else:
-            img = np.full((h, w, 3), 0.5, np.float32)
-        if img.shape[:2] != (h, w):
-            raise ValueError(f"view {ref_view}: image is {img.shape[:2]}, depth map is {(h, w)}")
-        colors.append((img[final_np] * 255).astype(np.uint8))
+        img = images[ref_view] if images is not None else pixels.pop(ref_view, None)
+        xyz, rgb = _host_points(ref_view, avg, final, k_ref, e_ref, img)
+        vertexs.append(xyz)
+        colors.append(rgb)
     write_ply(plyfilename, np.concatenate(vertexs, 0).astype(np.float32), np.concatenate(colors, 0))
     return stats
+
+
+def _host_points(ref_view: int, avg, final, k_ref, e_ref, img) -> Tuple[np.ndarray, np.ndarray]:
+    """eval.py:287-296 for one reference view with numpy on the downloaded maps: the surviving pixels -> (world coordinates [n,3]
+    float64, colours [n,3] uint8); ``img``: float RGB [H,W,3] in 0..1, None: mid grey"""
+    final_np = final.cpu().numpy().astype(bool)
+    h, w = final_np.shape
+    x, y = np.meshgrid(np.arange(0, w), np.arange(0, h))
+    x, y, d = x[final_np], y[final_np], avg.cpu().numpy()[final_np]
+    xyz_ref = np.matmul(np.linalg.inv(k_ref), np.vstack((x, y, np.ones_like(x))) * d)          # eval.py:291-292
+    xyz_world = np.matmul(np.linalg.inv(e_ref), np.vstack((xyz_ref, np.ones_like(x))))[:3]    # eval.py:293-294
+    if img is None:
+        img = np.full((h, w, 3), 0.5, np.float32)
+    if img.shape[:2] != (h, w):
+        raise ValueError(f"view {ref_view}: image is {img.shape[:2]}, depth map is {(h, w)}")
+    return xyz_world.transpose((1, 0)), (img[final_np] * 255).astype(np.uint8)

@@ -202,17 +202,9 @@ def _forward_cached(args, dataset, indices, model, dev, cache: ScanFeatureCache,
 
 
 def scan_cameras(scan_folder: str, views: Sequence[int], sizes: Dict[int, Tuple[int, int]], img_wh) -> dict:
-    """cams[view] = (K, E) with the intrinsics rescaled to the depth maps' size exactly as ``fusion.filter_depth`` does
-    (eval.py:231-232: python float times float32 row)"""
-    cams = {}
-    for v in views:
-        k, e = fusion.read_camera_parameters(os.path.join(scan_folder, "cams_1/{:0>8}_cam.txt".format(v)))
-        original_w, original_h = sizes[v]
-        k = k.copy()
-        k[0] *= img_wh[0] / original_w
-        k[1] *= img_wh[1] / original_h
-        cams[v] = (k, e)
-    return cams
+    """cams[view] = (K, E) with the intrinsics rescaled to the depth maps' size by the function ``fusion.filter_depth`` uses;
+    sizes[view] = (original_w, original_h)"""
+    return {v: fusion.read_scaled_camera(scan_folder, v, img_wh[0] / sizes[v][0], img_wh[1] / sizes[v][1]) for v in views}
 
 
 def fuse_scans_from_memory(args, dataset, scans: Sequence[str], model, dev) -> Dict[str, Dict[int, Tuple[float, float, float]]]:
@@ -245,14 +237,8 @@ def fuse_scans_from_memory(args, dataset, scans: Sequence[str], model, dev) -> D
             cams = scan_cameras(os.path.join(dataset.datapath, scan), views, store.size, img_wh)
             mask_folder = os.path.join(args.outdir, scan, "mask") if getattr(args, "save_masks", False) else None
             stats[scan] = fusion.fuse_scan(pairs, cams, store.depth, store.conf, store.rgb,
-                                           os.path.join(args.outdir, scan + ".ply"), args.geo_pixel_thres, args.geo_depth_thres,
-                                           args.photo_thres, args.geo_mask_thres, str(dev), mask_folder=mask_folder,
-                                           dedupe=bool(getattr(args, "fuse_dedupe", False)),
-                                           normals=bool(getattr(args, "ply_normals", False)),
-                                           normal_edge_thres=float(getattr(args, "normal_edge_thres", 0.01)),
-                                           mesh=fusion.mesh_options_from_args(args, os.path.join(args.outdir, scan + "_mesh.ply")),
-                                           **fusion.consistency_from_args(args))
-            for v, (g, ph, f) in stats[scan].items():
-                print("processing {}, ref-view{:0>2}, geo_mask:{:3f} photo_mask:{:3f} final_mask: {:3f}".format(scan, v, g, ph, f))
+                                           os.path.join(args.outdir, scan + ".ply"), device=str(dev), mask_folder=mask_folder,
+                                           **fusion.fuse_keywords_from_args(args, os.path.join(args.outdir, scan + "_mesh.ply")))
+            fusion.print_view_shares(scan, stats[scan])
             del store
     return stats
