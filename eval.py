@@ -155,9 +155,16 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--mesh_component_share", type=float, default=None, metavar="F",
                    help="--mesh: leave out the components with fewer than F x the triangles of the largest component, F in [0, 1]: "
                         "a threshold without a scale.  With --mesh_min_component a component must pass both.  No default")
+    p.add_argument("--mesh_simplify", type=float, default=None, metavar="F",
+                   help="--mesh: also write <outdir>/<scan>_mesh_simplified.ply, the mesh of <scan>_mesh.ply (after the component "
+                        "filter, if that is on) simplified on the GPU by vertex clustering with quadric placement: one vertex per "
+                        "occupied cell of F voxels' side, placed at the minimiser of the cell's plane quadrics, so corners and planes "
+                        "stay.  <scan>_mesh.ply and every other output byte stay as they are.  No default; 2 is a reasonable start "
+                        "(marching tetrahedra emit triangles far smaller than the depth noise)")
     p.add_argument("--mesh_budget_gb", type=float, default=16.0,
                    help="--mesh: GPU memory in GiB that the kept fused views (9 bytes per pixel and view), the volume, the extraction "
-                        "workspace, the mesh buffers and the component filter's labels, counts and workspace may take together; a larger request stops with the bytes it needs.  A choice")
+                        "workspace, the mesh buffers, the component filter's labels, counts and workspace and the simplifier's keys, "
+                        "sort orders, representatives and workspace may take together; a larger request stops with the bytes it needs.  A choice")
     p.add_argument("--clean_cloud", default=None, choices=["statistical", "radius"],
                    help="--filter: also write <outdir>/<scan>_clean.ply, the scan's cloud without its outliers (floaters: sky pixels, "
                         "specular surfaces, thin structures that pass the masks in a few views); <scan>.ply and every other output "
@@ -318,11 +325,16 @@ def check_ply_normals(args) -> bool:
 
 def check_mesh(args) -> bool:
     """--mesh needs --filter and the GPU point assembly; its numeric flags are checked where the options are built, before any work.
-    --mesh_min_component and --mesh_component_share need --mesh: an argparse error (usage, exit status 2) without it"""
+    --mesh_min_component, --mesh_component_share and --mesh_simplify need --mesh: an argparse error (usage, exit status 2) without it,
+    like a --mesh_simplify that is not above 0"""
     if not getattr(args, "mesh", False):
         for flag in ("mesh_min_component", "mesh_component_share"):
             if getattr(args, flag, None) is not None:
                 build_parser().error("--{} needs --mesh (it filters the mesh's connected components)".format(flag))
+        if getattr(args, "mesh_simplify", None) is not None:
+            build_parser().error("--mesh_simplify needs --mesh (it simplifies the mesh of <scan>_mesh.ply)")
+    if getattr(args, "mesh_simplify", None) is not None and not 0.0 < args.mesh_simplify < float("inf"):
+        build_parser().error("--mesh_simplify must be a finite cell side in voxels above 0, got {}".format(args.mesh_simplify))
     if not _check_gpu_assembly_flag(args, "mesh", "--mesh", "the volume is integrated from the fused depth maps that stay on the GPU"):
         return False
     from itermvs_amd import fusion

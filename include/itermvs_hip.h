@@ -914,6 +914,85 @@ int itermvs_mesh_keep(const uint8_t* vertices, int32_t NV, int32_t record_bytes,
                       int64_t face_capacity, uint64_t* totals, uint8_t* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Simplification of an indexed triangle mesh by vertex clustering with quadric placement (eval.py --mesh_simplify, simplify_mesh.py;
+ * csrc/mesh_simplify.hip; Lindstrom 2000, "Out-of-core simplification of large polygonal models"; no counterpart in the reference;
+ * numpy restatement: tests/mesh_simplify_reference.py; host side: itermvs_amd/fusion.py simplify_mesh).  Additions compatible with
+ * ABI 20.  vertices: device [NV] records of record_bytes (12..64; the mesh's is 15) bytes, unpadded; bytes 0..11 are float32 x, y, z,
+ * little-endian; a record of at least 15 bytes has red, green, blue in bytes 12..14.  faces: device [NF][3] int32.  The grid (origin
+ * ox, oy, oz; nx, ny, nz cells of side `cell`) and its key are those of itermvs_cloud_cell_keys below.  All arithmetic is fp64 on the
+ * float32 coordinates without contraction, sums are taken in the written order, division is IEEE; no float atomics, no workgroup
+ * waits on another, the host is not asked between the launches: the same input gives the same bytes on every run.
+ *   1. A vertex is VALID iff its three coordinates are finite and it lies inside the grid (its key is not INT64_MAX).
+ *   2. A face is VALID iff its three indices lie in [0, NV) and its three vertices are valid.
+ *   3. A cluster is the set of valid vertices of one cell.  Clusters are numbered in ascending cell key; inside a cluster the members
+ *      are in ascending vertex index.
+ *   4. The representative of a cluster with m members.  m == 1: the member's record, all record_bytes unchanged.  m > 1:
+ *      mu.x = sx / (double)m with sx = 0.0; sx = sx + x_k over the members in order (y, z alike).  record_bytes >= 15: each colour
+ *      channel is rint((double)(integer sum over the members) / (double)m) as uint8.  Every other byte from the 12th on is copied
+ *      from the lowest member.  Over every valid face with at least one corner in the cluster, once each, in ascending face index,
+ *      with a, b, c its three ORIGINAL positions, u = b - a, v = c - a:
+ *        n.x = (u.y*v.z) - (u.z*v.y); n.y = (u.z*v.x) - (u.x*v.z); n.z = (u.x*v.y) - (u.y*v.x)   (unnormalised: weight = area^2)
+ *        h = ((n.x*(a.x - mu.x)) + (n.y*(a.y - mu.y))) + (n.z*(a.z - mu.z))
+ *        Axx += n.x*n.x; Axy += n.x*n.y; Axz += n.x*n.z; Ayy += n.y*n.y; Ayz += n.y*n.z; Azz += n.z*n.z;
+ *        r.x += n.x*h; r.y += n.y*h; r.z += n.z*h                                              (all nine sums start at 0.0)
+ *      trace = (Axx + Ayy) + Azz; lambda = ITERMVS_MESH_SIMPLIFY_REG * trace (1e-3: a choice of Lindstrom's order of magnitude, not
+ *      a measured optimum); a00 = Axx + lambda, a11 = Ayy + lambda, a22 = Azz + lambda; the cofactors
+ *        c00 = (a11*a22) - (Ayz*Ayz); c01 = (Axz*Ayz) - (Axy*a22); c02 = (Axy*Ayz) - (Axz*a11);
+ *        c11 = (a00*a22) - (Axz*Axz); c12 = (Axy*Axz) - (a00*Ayz); c22 = (a00*a11) - (Axy*Axy);
+ *      det = ((a00*c00) + (Axy*c01)) + (Axz*c02);
+ *        y.x = (((c00*r.x) + (c01*r.y)) + (c02*r.z)) / det; y.y = (((c01*r.x) + (c11*r.y)) + (c12*r.z)) / det;
+ *        y.z = (((c02*r.x) + (c12*r.y)) + (c22*r.z)) / det.
+ *      y = 0 if trace == 0, if det is not finite or not > 0, or if a component of y is not finite.  Per axis, with i the cell's
+ *      index on it, lo = o + (double)i*cell, hi = o + (double)(i + 1)*cell: x = mu + y; x < lo ? lo : (x > hi ? hi : x), converted
+ *      to float32 once.
+ *   5. A valid face becomes its three cluster numbers in its own corner order.  It is dropped if two of them are equal, or if an
+ *      earlier surviving face has the same triple up to cyclic rotation (the same orientation; the opposite orientation is another
+ *      face and stays).  Survivors stay in ascending original face index.
+ *   6. The output vertices are the representatives of the clusters that a surviving face references, in ascending cluster number;
+ *      the faces are renumbered to match.  No unreferenced vertex is written.
+ * The sorts between the entry points are the caller's and must be STABLE (itermvs_amd/fusion.py simplify_mesh: torch.sort):
+ *   keys_sorted, perm: the vertices' keys ascending and perm int64 [NV] = the vertex at each sorted position; cluster_sorted int32
+ *   [NV] = the inclusive prefix sum of itermvs_cloud_voxel_heads(keys_sorted) minus 1, or -1 where the key is INT64_MAX; cluster int32
+ *   [NV] = the same per vertex (cluster[perm[i]] = cluster_sorted[i]).
+ *
+ * itermvs_mesh_simplify_corners -- one launch.  pair_cluster int32 [NF][3] = the cluster of each corner of a valid face, 2^31 - 1
+ *   three times for an invalid one.  A face is ALIVE iff it is valid and its three clusters differ; its canonical triple (c0, c1, c2)
+ *   is the cyclic rotation that starts at the smallest.  key_hi int64 [NF] = (c0 << 32) | c1, INT64_MAX unless alive; key_lo int32
+ *   [NF] = c2, 2^31 - 1 unless alive.  The caller sorts the 3*NF pairs (pair_cluster flat, index e = 3*face + corner: face-major)
+ *   by cluster into pair_sorted and pair_face[e] = the face of the pair now at e, and the faces by (key_hi, key_lo) into
+ *   key_hi_sorted, key_lo_sorted and order int32 [NF] = the face at each sorted position.
+ * itermvs_mesh_simplify_clusters -- one launch, rule 4: reps: device [NV] records; record c is the representative of cluster c (the
+ *   records from the number of clusters on are not written).  The thread at the head of each run of cluster_sorted walks the run and
+ *   then the cluster's run of pair_sorted, found by binary search, skipping a pair whose face equals the pair's before it.
+ * itermvs_mesh_simplify_emit -- rules 5 and 6.  A memset of the marks and six launches (mark: the head of each run of equal sorted
+ *   triples survives and marks its three clusters, plain byte stores of the constant 1; per-256 count of the clusters, of the faces;
+ *   one-workgroup scan; vertex scatter; face scatter).  Capacities and totals (device uint64 [2] = vertices, faces) as for
+ *   itermvs_tsdf_mesh: a vertex or face whose number is >= its capacity is not stored, totals holds the true counts all the same, the
+ *   stored faces hold the true new indices; nothing outside out_vertices[0 : record_bytes*vertex_capacity], out_faces[0 :
+ *   3*face_capacity], totals and the workspace is written.  workspace: the *bytes of itermvs_mesh_simplify_emit_workspace_bytes(NV,
+ *   NF, bytes) (8 per 256 vertices and per 256 faces + 5 per vertex + 1 per face, rounded up to 8), 8-byte aligned.
+ * Validation before any HIP call, all three: ITERMVS_ERR_NULL for a NULL pointer (the per-vertex arrays may be NULL iff NV == 0, the
+ *   per-face arrays iff NF == 0, out_vertices / out_faces iff their capacity is 0; totals and workspace never); ITERMVS_ERR_DIMS for
+ *   NV < 0, NF < 0, NF > (2^31 - 1) / 3 (the pairs are indexed in an int32), record_bytes outside 12..64, cell not finite or not > 0,
+ *   a non-finite origin, a grid dimension outside 1..2^21, a capacity < 0 and vertex_capacity > 2^31 - 1; ITERMVS_ERR_ALIGN for the
+ *   workspace.  NV == 0 and NF == 0 are legal: emit writes totals = {0, 0} and nothing else.  No content of a mesh (NaN or huge
+ *   coordinates, indices of -1 or 2^31 - 1) makes a kernel read or write outside its buffers, and every index taken from one of the
+ *   caller's arrays is compared with its range before use: arrays that do not describe the mesh give a wrong mesh, nothing worse.
+ * ------------------------------------------------------------------------------------------ */
+#define ITERMVS_MESH_SIMPLIFY_REG 1e-3
+int itermvs_mesh_simplify_corners(const int32_t* faces, int64_t NF, int32_t NV, const int32_t* cluster, int32_t* pair_cluster,
+                                  int64_t* key_hi, int32_t* key_lo, void* stream);
+int itermvs_mesh_simplify_clusters(const uint8_t* vertices, int32_t NV, int32_t record_bytes, const int32_t* faces, int64_t NF,
+                                   const int64_t* keys_sorted, const int64_t* perm, const int32_t* cluster_sorted,
+                                   const int32_t* pair_sorted, const int32_t* pair_face, double ox, double oy, double oz, int32_t nx,
+                                   int32_t ny, int32_t nz, double cell, uint8_t* reps, void* stream);
+int itermvs_mesh_simplify_emit_workspace_bytes(int32_t NV, int64_t NF, int64_t* bytes /* host */);
+int itermvs_mesh_simplify_emit(const uint8_t* reps, int32_t NV, int32_t record_bytes, const int32_t* faces, int64_t NF,
+                               const int32_t* cluster, const int64_t* key_hi_sorted, const int32_t* key_lo_sorted, const int32_t* order,
+                               uint8_t* out_vertices, int64_t vertex_capacity, int32_t* out_faces, int64_t face_capacity,
+                               uint64_t* totals, uint8_t* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The COLMAP converter's two device stages (csrc/colmap.hip; colmap_input.py of the reference, host side: itermvs_amd/colmap.py).
  * Common inputs (device): the images' observation lists as CSR -- offsets [V+1] int64 ascending, point [offsets[V]] int32 = dense
  *   point index into xyz or -1, in file order (image index = position in images.bin) -- and xyz [P][3] fp64.  An entry outside

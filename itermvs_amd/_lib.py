@@ -223,6 +223,12 @@ PROTOTYPES = {
     "itermvs_mesh_keep_workspace_bytes": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
     "itermvs_mesh_keep": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
                                     C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "itermvs_mesh_simplify_corners": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 5),
+    "itermvs_mesh_simplify_clusters": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64] + [C.c_void_p] * 5 +
+                                       [C.c_double] * 3 + [C.c_int32] * 3 + [C.c_double, C.c_void_p, C.c_void_p]),
+    "itermvs_mesh_simplify_emit_workspace_bytes": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
+    "itermvs_mesh_simplify_emit": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64] + [C.c_void_p] * 5 +
+                                   [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "itermvs_view_scores": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p,
                                       C.c_void_p]),
     "itermvs_depth_ranges": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -260,7 +260,9 @@ class MeshOptions:
     min_count: views a voxel needs to be valid.  budget_bytes: GPU memory the kept views, the volume, the extraction workspace and
     the mesh buffers may take together.  batch_views: views per integrate launch.  The defaults are choices, not measured optima.
     min_component (triangles) and component_share (of the largest component's triangles, in [0, 1]): the connected components of the
-    mesh with fewer triangles than ``mesh_min_faces`` makes of the two are left out of the file; both 0: no filter, no kernel."""
+    mesh with fewer triangles than ``mesh_min_faces`` makes of the two are left out of the file; both 0: no filter, no kernel.
+    simplify_voxels: 0: nothing more; above 0: the mesh of ``path`` is also simplified by ``simplify_mesh`` with cells of that many
+    voxels and written to ``simplified_path(path)``; ``path`` itself keeps its bytes."""
     path: str
     bounds: Optional[Sequence[float]] = None
     bounds_quantile: float = 0.01
@@ -272,6 +274,12 @@ class MeshOptions:
     batch_views: int = MESH_INTEGRATE_BATCH
     min_component: int = 0
     component_share: float = 0.0
+    # an attribute beside the fields, set by the constructor: dataclasses.asdict, == and the field list describe <path> itself, as
+    # before; the second file is an addition to it (dataclasses.replace() must be given the value again: mesh_options does)
+    simplify_voxels: dataclasses.InitVar[float] = 0.0
+
+    def __post_init__(self, simplify_voxels):
+        self.simplify_voxels = simplify_voxels
 
 
 def mesh_options(mesh) -> Optional[MeshOptions]:
@@ -284,7 +292,7 @@ def mesh_options(mesh) -> Optional[MeshOptions]:
         b = tuple(float(x) for x in m.bounds)
         if len(b) != 6 or not all(finite(x) for x in b) or not all(b[i] < b[i + 3] for i in range(3)):
             raise ValueError(f"mesh: bounds must be six finite numbers x0 y0 z0 x1 y1 z1 with x0 < x1, y0 < y1, z0 < z1, got {m.bounds}")
-        m = dataclasses.replace(m, bounds=b)
+        m = dataclasses.replace(m, bounds=b, simplify_voxels=m.simplify_voxels)
     if not 0 <= m.bounds_quantile < 0.5:
         raise ValueError(f"mesh: bounds_quantile must be in [0, 0.5), got {m.bounds_quantile}")
     if m.voxel is not None and not (finite(m.voxel) and m.voxel > 0):
@@ -300,6 +308,10 @@ def mesh_options(mesh) -> Optional[MeshOptions]:
     problem = component_problem(m.min_component, m.component_share)
     if problem:
         raise ValueError("mesh: " + problem)
+    if m.simplify_voxels != 0:
+        problem = simplify_problem(m.simplify_voxels)
+        if problem:
+            raise ValueError("mesh: " + problem.replace("cell", "simplify_voxels", 1))
     return m
 
 
@@ -311,6 +323,27 @@ def component_problem(min_component, component_share) -> Optional[str]:
             or not 0.0 <= float(component_share) <= 1.0:
         return f"component_share must be a number in [0, 1], got {component_share!r}"
     return None
+
+
+def simplify_problem(cell, origin=None) -> Optional[str]:
+    """what is wrong with the cell side and the origin of ``simplify_mesh``, or None"""
+    number = lambda x: not isinstance(x, bool) and isinstance(x, (int, float, np.integer, np.floating))      # noqa: E731
+    if not number(cell) or not 0.0 < float(cell) < float("inf"):
+        return f"cell must be a finite number above 0, got {cell!r}"
+    if origin is not None:
+        try:
+            o = tuple(origin)
+        except TypeError:
+            o = ()
+        if len(o) != 3 or not all(number(x) and -float("inf") < float(x) < float("inf") for x in o):
+            return f"origin must be three finite numbers, got {origin!r}"
+    return None
+
+
+def simplified_path(path: str) -> str:
+    """<scan>_mesh.ply -> <scan>_mesh_simplified.ply"""
+    stem, ext = os.path.splitext(path)
+    return stem + "_simplified" + ext
 
 
 def mesh_min_faces(min_component: int, component_share: float, largest: int) -> int:
@@ -328,7 +361,8 @@ def mesh_options_from_args(args, path: str) -> Optional[MeshOptions]:
                                     min_count=getattr(args, "mesh_min_count", 2),
                                     budget_bytes=int(getattr(args, "mesh_budget_gb", 16.0) * (1 << 30)),
                                     min_component=getattr(args, "mesh_min_component", None) or 0,
-                                    component_share=getattr(args, "mesh_component_share", None) or 0.0))
+                                    component_share=getattr(args, "mesh_component_share", None) or 0.0,
+                                    simplify_voxels=0.0 if getattr(args, "mesh_simplify", None) is None else args.mesh_simplify))
 
 
 def mesh_bounds(xyz, quantile: float) -> Tuple[float, ...]:
@@ -468,6 +502,116 @@ def keep_mesh_components(vertices: torch.Tensor, faces: torch.Tensor, min_compon
     return out_vertices, out_faces
 
 
+SIMPLIFY_SORT_BYTES_PER_VERTEX = 64        # coordinates, keys, sorted keys, order, heads, prefix sums, cluster numbers (twice)
+SIMPLIFY_SORT_BYTES_PER_FACE = 148         # the 3 pairs (values, sorted values, order, faces), the triple keys and their two sorts
+
+
+def simplify_grid(xyz: torch.Tensor, cell: float, origin=None) -> ops.CloudGrid:
+    """the grid of ``simplify_mesh`` over float32 [n,3] coordinates: ``origin`` or, for None, the per-axis minimum of the finite
+    vertices (exact: a float32 as a double); cells up to the finite vertices' maximum.  One synchronisation (the extent comes to the
+    host, as in ``cloud_grid.grid_for``); more than 2^21 cells on an axis raise"""
+    from . import cloud_grid
+    finite = torch.isfinite(xyz).all(1)
+    inf = float("inf")
+    lo = torch.where(finite[:, None], xyz, torch.full_like(xyz, inf)).min(0).values.double()
+    hi = torch.where(finite[:, None], xyz, torch.full_like(xyz, -inf)).max(0).values.double()
+    lo, hi = torch.stack([lo, hi]).tolist()
+    if not all(-inf < v < inf for v in lo):                           # no finite vertex
+        return ops.CloudGrid(tuple(float(o) for o in origin) if origin is not None else (0.0, 0.0, 0.0), (1, 1, 1), float(cell))
+    o = [float(v) for v in (lo if origin is None else origin)]
+    dims = [max(1, int(math.floor((hi[a] - o[a]) / float(cell))) + 1) for a in range(3)]
+    if max(dims) > cloud_grid.MAX_CELL_DIM:
+        raise ValueError(f"simplify_mesh: the mesh spans {dims} cells of side {cell}; at most {cloud_grid.MAX_CELL_DIM} per axis fit "
+                         "the cell key (choose a larger cell)")
+    return ops.CloudGrid(tuple(o), tuple(dims), float(cell))
+
+
+def simplify_clusters(vertices: torch.Tensor, flat: torch.Tensor, rec: int, xyz: torch.Tensor, grid: ops.CloudGrid):
+    """everything of ``simplify_mesh`` before the compaction, nothing read back: the three stable sorts and the two launches
+    between them -> (reps, cluster, key_hi_sorted, key_lo_sorted, order: the arguments of ``ops.mesh_simplify_emit``; counts: a
+    function that reads clusters, valid and alive faces back)"""
+    nv, dev = xyz.shape[0], flat.device
+    none = torch.iinfo(torch.int64).max
+    keys_sorted, perm = torch.sort(ops.cloud_cell_keys(xyz, grid), stable=True)
+    cluster_sorted = torch.where(keys_sorted != none, torch.cumsum(ops.cloud_voxel_heads(keys_sorted), 0) - 1, -1).to(torch.int32)
+    cluster = torch.empty(nv, device=dev, dtype=torch.int32)
+    cluster[perm] = cluster_sorted
+    pair, key_hi, key_lo = ops.mesh_simplify_corners(flat, cluster)
+    pair_sorted, pair_order = torch.sort(pair, stable=True)                    # face-major pairs, by cluster
+    pair_face = torch.div(pair_order, 3, rounding_mode="floor").to(torch.int32)
+    by_lo = torch.sort(key_lo, stable=True).indices                            # the canonical triples: by c2, then by (c0, c1)
+    key_hi_sorted, by_hi = torch.sort(key_hi[by_lo], stable=True)
+    order = by_lo[by_hi]
+    key_lo_sorted, order = key_lo[order], order.to(torch.int32)
+    reps = ops.mesh_simplify_clusters(vertices, rec, flat, keys_sorted, perm, cluster_sorted, pair_sorted, pair_face, grid)
+
+    def counts():
+        nf = key_hi.numel()
+        return (int(cluster_sorted.max()) + 1 if nv else 0, int((pair[0::3] != 0x7fffffff).sum()) if nf else 0,
+                int((key_hi != none).sum()) if nf else 0)
+
+    return reps, cluster, key_hi_sorted, key_lo_sorted, order, counts
+
+
+def simplify_mesh(vertices: torch.Tensor, faces: torch.Tensor, cell: float, origin=None, info: dict = None, budget_bytes: int = None,
+                  used_bytes: int = 0, record_bytes: int = ops.MESH_VERTEX_BYTES, dims=None):
+    """vertex clustering with quadric placement on the GPU (include/itermvs_hip.h: rules 1..6): vertex bytes uint8
+    [nv*record_bytes] and faces int32 [nf*3], as ``extract_mesh`` returns them -> (vertices, faces) of the same form, one vertex per
+    occupied cell of side ``cell`` that a surviving triangle references.  ``origin``: the grid's corner; None: the per-axis minimum
+    of the valid vertices.  ``dims``: the grid's cells per axis, with ``origin``; None: up to the vertices' maximum.
+    The three stable sorts (vertices by cell key, the 3 nf (cluster, face) pairs by cluster, the canonical triples) are torch.sort; keys
+    and run heads are ``itermvs_cloud_cell_keys`` / ``itermvs_cloud_voxel_heads``; the rest is ``itermvs_mesh_simplify_*``, the last of
+    them twice like ``extract_mesh``.  One synchronisation for the extent and one for the totals.  The buffers are checked against
+    what the budget has left before they are allocated.  ``info`` receives the counts, ``cell`` and ``origin``."""
+    problem = simplify_problem(cell, origin)
+    if problem:
+        raise ValueError("simplify_mesh: " + problem)
+    if dims is not None and origin is None:
+        raise ValueError("simplify_mesh: dims needs an origin")
+    dev, rec = faces.device, int(record_bytes)
+    if not 12 <= rec <= 64 or vertices.numel() % rec or faces.numel() % 3:
+        raise ValueError(f"simplify_mesh: {vertices.numel()} vertex bytes are no records of {rec} bytes (12..64), or {faces.numel()} "
+                         "indices no triples")
+    nv, nf = vertices.numel() // rec, faces.numel() // 3
+    if nf > ops.MESH_SIMPLIFY_MAX_FACES:
+        raise ValueError(f"simplify_mesh: {nf} triangles are beyond the {ops.MESH_SIMPLIFY_MAX_FACES} of one launch")
+    sort_bytes = SIMPLIFY_SORT_BYTES_PER_VERTEX * nv + SIMPLIFY_SORT_BYTES_PER_FACE * nf
+    reps_bytes, workspace_bytes = rec * nv, ops.mesh_simplify_emit_workspace_bytes(nv, nf)
+    own_bytes = sort_bytes + reps_bytes + workspace_bytes
+    hint = "lower --mesh_resolution, raise --mesh_voxel or raise --mesh_budget_gb"
+    if budget_bytes is not None and used_bytes + own_bytes > budget_bytes:
+        raise ValueError(f"mesh: the simplifier of {nv} vertices and {nf} triangles needs {sort_bytes} bytes of keys and sort orders, "
+                         f"{reps_bytes} of representatives and {workspace_bytes} of workspace on top of {used_bytes}, the budget is "
+                         f"{budget_bytes}; {hint}")
+    flat = faces.reshape(-1)
+    xyz = vertices.view(nv, rec)[:, :12].contiguous().view(torch.float32) if nv else torch.empty((0, 3), device=dev, dtype=torch.float32)
+    if nv:
+        grid = simplify_grid(xyz, cell, origin) if dims is None else ops.CloudGrid(tuple(float(o) for o in origin),
+                                                                                   tuple(int(d) for d in dims), float(cell))
+    else:
+        grid = ops.CloudGrid(tuple(float(o) for o in origin) if origin is not None else (0.0, 0.0, 0.0), (1, 1, 1), float(cell))
+    reps, cluster, key_hi_sorted, key_lo_sorted, order, counts = simplify_clusters(vertices, flat, rec, xyz, grid)
+    workspace = torch.empty(max(workspace_bytes, 8), device=dev, dtype=torch.uint8)
+    totals = torch.zeros(2, device=dev, dtype=torch.int64)
+
+    def check(kv, kf, out_bytes):
+        if budget_bytes is not None and used_bytes + own_bytes + out_bytes > budget_bytes:
+            raise ValueError(f"mesh: the simplified {kv} vertices and {kf} triangles need {out_bytes} bytes on top of {used_bytes} and "
+                             f"the simplifier's {own_bytes} (keys and sort orders, representatives, workspace), the budget is "
+                             f"{budget_bytes}; {hint}")
+
+    out_vertices, out_faces = _count_then_fill(
+        lambda v, f: ops.mesh_simplify_emit(reps, rec, flat, cluster, key_hi_sorted, key_lo_sorted, order, v, f, totals, workspace),
+        totals, rec, check)
+    if info is not None:
+        clusters, valid_faces, alive = counts()
+        info.update(vertices_before=nv, faces_before=nf, vertices=out_vertices.numel() // rec, faces=out_faces.numel() // 3,
+                    clusters=clusters, valid_faces=valid_faces, degenerate_faces=valid_faces - alive,
+                    duplicate_faces=alive - out_faces.numel() // 3, cell=float(cell), origin=tuple(grid.origin), dims=tuple(grid.dims),
+                    simplify_bytes=own_bytes)
+    return out_vertices, out_faces
+
+
 def write_scan_mesh(mesh: MeshOptions, bounds: Sequence[float], depth: torch.Tensor, mask: torch.Tensor, cams: torch.Tensor,
                     rgb: torch.Tensor, info: dict = None) -> None:
     """the kept views (depth float64 [V,H,W], mask uint8 [V,H,W], cams float32 [V,21] = K | E[:3], rgb uint8 [V,H,W,3], on the GPU, in
@@ -496,6 +640,24 @@ def write_scan_mesh(mesh: MeshOptions, bounds: Sequence[float], depth: torch.Ten
         info.update(plan, bounds=tuple(bounds), vertices=vertices.numel() // ops.MESH_VERTEX_BYTES, faces=faces.numel() // 3,
                     batches=(v + int(mesh.batch_views) - 1) // int(mesh.batch_views))
         info.update(kept_info)
+    if mesh.simplify_voxels:
+        simplified = write_simplified_mesh(mesh.path, vertices, faces, float(mesh.simplify_voxels) * plan["voxel"], mesh.budget_bytes,
+                                           plan["need_bytes"] + vertices.numel() + faces.numel() * 4)
+        if info is not None:
+            info.update(simplified=simplified)
+
+
+def write_simplified_mesh(path: str, vertices: torch.Tensor, faces: torch.Tensor, cell: float, budget_bytes: int = None,
+                          used_bytes: int = 0) -> dict:
+    """the mesh that ``path`` holds (on the GPU) -> ``simplified_path(path)`` by ``simplify_mesh`` with the default origin, and one
+    printed line with both triangle counts and the cell in world units as ``repr``: ``simplify_mesh.py --cell`` with that number
+    repeats the file.  -> the simplifier's ``info``"""
+    info = {}
+    out_vertices, out_faces = simplify_mesh(vertices, faces, cell, info=info, budget_bytes=budget_bytes, used_bytes=used_bytes)
+    write_ply_mesh(simplified_path(path), out_vertices.cpu().numpy(), out_faces.cpu().numpy())
+    print("simplified {}: {} -> {} triangles, {} -> {} vertices, cell {!r}, wrote {}".format(
+        path, info["faces_before"], info["faces"], info["vertices_before"], info["vertices"], info["cell"], simplified_path(path)))
+    return info
 
 
 class _DeviceScan:
@@ -634,6 +796,8 @@ class _MeshKeeper:
         info = {}
         if not self.pairs:
             write_ply_mesh(self.mesh.path, np.zeros(0, MESH_VERTEX), np.zeros((0, 3), np.int32))
+            if self.mesh.simplify_voxels:
+                write_ply_mesh(simplified_path(self.mesh.path), np.zeros(0, MESH_VERTEX), np.zeros((0, 3), np.int32))
             return info
         bounds = self.mesh.bounds
         if bounds is None:

@@ -1606,6 +1606,98 @@ def mesh_keep(vertices: Tensor, record_bytes: int, faces: Tensor, label: Tensor,
                                         totals.data_ptr(), workspace.data_ptr(), _stream()), "itermvs_mesh_keep")
 
 
+MESH_SIMPLIFY_REG = 1e-3           # include/itermvs_hip.h: ITERMVS_MESH_SIMPLIFY_REG
+MESH_SIMPLIFY_MAX_FACES = (2 ** 31 - 1) // 3
+
+
+def _simplify_sizes(what: str, named: Sequence[tuple]) -> None:
+    """the checks the three simplify wrappers share: every (name, tensor, dtype, elements or None) is a contiguous device tensor of
+    that dtype and size"""
+    for name, t, dtype, n in named:
+        _tsdf_tensor(what, name, t, dtype)
+        if n is not None and t.numel() != n:
+            raise RuntimeError(f"{what}: {name} must have {n} elements, got {t.numel()}")
+
+
+def mesh_simplify_corners(faces: Tensor, cluster: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """itermvs_mesh_simplify_corners: ``faces`` int32 [NF*3], ``cluster`` int32 [NV] (the cluster of every vertex, -1: not valid) ->
+    (pair_cluster int32 [NF*3], key_hi int64 [NF], key_lo int32 [NF]); nothing is read back"""
+    what = "mesh_simplify_corners"
+    _simplify_sizes(what, (("faces", faces, torch.int32, None), ("cluster", cluster, torch.int32, None)))
+    if faces.numel() % 3:
+        raise RuntimeError(f"{what}: {faces.numel()} indices are no triples")
+    nf, nv, dev = faces.numel() // 3, cluster.numel(), faces.device
+    pair = torch.empty(3 * nf, device=dev, dtype=torch.int32)
+    hi = torch.empty(nf, device=dev, dtype=torch.int64)
+    lo = torch.empty(nf, device=dev, dtype=torch.int32)
+    if nf:
+        check(_lib.load().itermvs_mesh_simplify_corners(faces.data_ptr(), nf, nv, cluster.data_ptr() if nv else None, pair.data_ptr(),
+                                                        hi.data_ptr(), lo.data_ptr(), _stream()), "itermvs_mesh_simplify_corners")
+    return pair, hi, lo
+
+
+def mesh_simplify_clusters(vertices: Tensor, record_bytes: int, faces: Tensor, keys_sorted: Tensor, perm: Tensor, cluster_sorted: Tensor,
+                           pair_sorted: Tensor, pair_face: Tensor, grid: "CloudGrid", reps: Optional[Tensor] = None) -> Tensor:
+    """itermvs_mesh_simplify_clusters: the representative record of every cluster -> ``reps`` uint8 [NV*record_bytes] (record c =
+    cluster c; allocated here when not given).  The arrays are those of the header, sorted stably by the caller."""
+    what = "mesh_simplify_clusters"
+    rec = int(record_bytes)
+    _simplify_sizes(what, (("vertices", vertices, torch.uint8, None), ("faces", faces, torch.int32, None)))
+    if rec < 1 or vertices.numel() % rec or faces.numel() % 3:
+        raise RuntimeError(f"{what}: {vertices.numel()} vertex bytes are no records of {rec} bytes, or {faces.numel()} indices no triples")
+    nv, nf, dev = vertices.numel() // rec, faces.numel() // 3, vertices.device
+    if reps is None:
+        reps = torch.empty(nv * rec, device=dev, dtype=torch.uint8)
+    _simplify_sizes(what, (("keys_sorted", keys_sorted, torch.int64, nv), ("perm", perm, torch.int64, nv),
+                           ("cluster_sorted", cluster_sorted, torch.int32, nv), ("pair_sorted", pair_sorted, torch.int32, 3 * nf),
+                           ("pair_face", pair_face, torch.int32, 3 * nf), ("reps", reps, torch.uint8, nv * rec)))
+    at = lambda t, n: t.data_ptr() if n else None                  # noqa: E731  (an empty tensor has no address)
+    check(_lib.load().itermvs_mesh_simplify_clusters(at(vertices, nv), nv, rec, at(faces, nf), nf, at(keys_sorted, nv), at(perm, nv),
+                                                     at(cluster_sorted, nv), at(pair_sorted, nf), at(pair_face, nf), *grid.args(),
+                                                     at(reps, nv), _stream()), "itermvs_mesh_simplify_clusters")
+    return reps
+
+
+def mesh_simplify_emit_workspace_bytes(n_vertices: int, n_faces: int) -> int:
+    n = C.c_int64(0)
+    check(_lib.load().itermvs_mesh_simplify_emit_workspace_bytes(int(n_vertices), int(n_faces), C.byref(n)),
+          "itermvs_mesh_simplify_emit_workspace_bytes")
+    return int(n.value)
+
+
+def mesh_simplify_emit(reps: Tensor, record_bytes: int, faces: Tensor, cluster: Tensor, key_hi_sorted: Tensor, key_lo_sorted: Tensor,
+                       order: Tensor, out_vertices: Tensor, out_faces: Tensor, totals: Tensor, workspace: Optional[Tensor] = None,
+                       vertex_capacity: Optional[int] = None, face_capacity: Optional[int] = None) -> None:
+    """itermvs_mesh_simplify_emit: the surviving faces (renumbered) and the representatives they reference -> ``out_vertices``,
+    ``out_faces`` and ``totals`` (int64 [2]: vertices, faces, whatever the capacities); nothing is read back.  The capacities default
+    to all of the two buffers; ``workspace``: uint8 scratch of mesh_simplify_emit_workspace_bytes, allocated here when not given."""
+    what = "mesh_simplify_emit"
+    rec = int(record_bytes)
+    _simplify_sizes(what, (("reps", reps, torch.uint8, None), ("faces", faces, torch.int32, None),
+                           ("out_vertices", out_vertices, torch.uint8, None), ("out_faces", out_faces, torch.int32, None),
+                           ("totals", totals, torch.int64, 2)))
+    if rec < 1 or reps.numel() % rec or faces.numel() % 3:
+        raise RuntimeError(f"{what}: {reps.numel()} bytes are no records of {rec} bytes, or {faces.numel()} indices no triples")
+    nv, nf = reps.numel() // rec, faces.numel() // 3
+    _simplify_sizes(what, (("cluster", cluster, torch.int32, nv), ("key_hi_sorted", key_hi_sorted, torch.int64, nf),
+                           ("key_lo_sorted", key_lo_sorted, torch.int32, nf), ("order", order, torch.int32, nf)))
+    vcap = out_vertices.numel() // rec if vertex_capacity is None else int(vertex_capacity)
+    fcap = out_faces.numel() // 3 if face_capacity is None else int(face_capacity)
+    if vcap < 0 or vcap * rec > out_vertices.numel() or fcap < 0 or fcap * 3 > out_faces.numel():
+        raise RuntimeError(f"{what}: capacities {vcap} vertices, {fcap} triangles do not fit the buffers "
+                           f"({out_vertices.numel()} bytes, {out_faces.numel()} indices)")
+    need = mesh_simplify_emit_workspace_bytes(nv, nf)
+    if workspace is None:
+        workspace = torch.empty(max(need, 8), device=faces.device, dtype=torch.uint8)
+    elif not workspace.is_cuda or workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous():
+        raise RuntimeError(f"{what}: workspace must be a contiguous uint8 CUDA/ROCm tensor of >= {need} bytes")
+    at = lambda t, n: t.data_ptr() if n else None                  # noqa: E731
+    check(_lib.load().itermvs_mesh_simplify_emit(at(reps, nv), nv, rec, at(faces, nf), nf, at(cluster, nv), at(key_hi_sorted, nf),
+                                                 at(key_lo_sorted, nf), at(order, nf), at(out_vertices, vcap), vcap,
+                                                 at(out_faces, fcap), fcap, totals.data_ptr(), workspace.data_ptr(), _stream()),
+          "itermvs_mesh_simplify_emit")
+
+
 def _colmap_inputs(what: str, offsets: Tensor, point: Tensor, xyz: Tensor, per_view: Tensor, width: int) -> Tuple[int, int]:
     """shared checks of view_scores / depth_ranges -> (V, P).  ``offsets`` is the one HOST tensor: its values are checked here
     (ascending from offsets[0] >= 0 to offsets[V] <= len(point)), which the kernels rely on for their reads of ``point``."""
